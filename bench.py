@@ -8,11 +8,14 @@ MI355X".  One step = one spec_decode_flat launch over a rank's whole batch (1M r
 all ranks / max-over-ranks time.  `--gpus N` without a torchrun environment starts the N rank
 processes itself (spawned before anything touches a GPU).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`--dump-outputs
+DIR` also writes what the last timed step decoded).  Everything below runs only with `--full`.
+
 Extra legs (keys beside the headline): BASELINE config 5 (a 16M-record batch sharded over the
 ranks, decode-only and decode + one packed RCCL gather of all columns to rank 0), the generic
 (non-specialised) decode kernel, encode, nested (config 4), the PCIe-inclusive end-to-end
 decode from pinned host memory, the mpx frame index, LZ4, and the CPU oracle timed on the
-host (rank 0, N=1 only).  Every run checks a 200k-record sample of the headline batch against
+host (rank 0, N=1 only).  Every --full run checks a 200k-record sample of the headline batch against
 the oracle (decode columns/status and the encoder's bytes), outside the timed region.
 
 Input generation uses numpy + this engine's GPU encoder; the oracle is only the checker and the
@@ -39,6 +42,8 @@ METRIC = "Mmsg/s + GB/s decode (device-resident), 1M×256B batch, 1/2/4/8 MI355X
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md, chip-level parameters)
 COLUMN_BYTES = 122     # Flat16 decoded columns per record (spec_amd.FLAT16.column_bytes)
 VERIFY_RECORDS = 200_000
+DUMP_RECORDS = 1 << 16  # --dump-outputs: sampled records (x 123 column + status bytes as float32 = 32 MB)
+DUMP_SEED = 20240607
 SHARD_BLOCK = 1 << 21  # config 5: the 16M batch is 8 blocks of 2M records (one decode call each)
 
 
@@ -49,6 +54,11 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--records", type=int, default=1 << 20, help="records per GPU")
     p.add_argument("--seed", type=int, default=workload.SEED)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: per-launch kernel times + roofline, the oracle check, every extra leg "
+                        "and the CPU baselines (the --no-* options below trim this part)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step decoded (columns + status) as DIR/<name>.npy")
     p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     p.add_argument("--no-extras", action="store_true", help="skip encode / end-to-end legs")
     p.add_argument("--no-verify", action="store_true", help="skip the oracle check of a 200k-record sample")
@@ -229,6 +239,33 @@ def time_decode(dec, steps, warmup, dist):
         dec()
     barrier(dist)
     return time.perf_counter() - t0
+
+
+def dump_outputs(path, cols, status, rank, world):
+    """--dump-outputs: the decoded columns and status of the last timed step as float32 .npy files
+    (one value per column byte, exact), for a fixed seeded sample of DUMP_RECORDS records over all
+    ranks (all of them in a smaller batch), so two builds can be compared output for output.  With
+    several ranks every rank writes its own files (rank<k>_<name>.npy).  sample_index.npy
+    holds the sampled record numbers; column_sums.npy the float64 sum of every column byte lane
+    (the 16 columns back to back, then status) over the WHOLE batch, exact below 2^53."""
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    n = status.numel()
+    m = DUMP_RECORDS // world  # every rank writes its share: 32 MB in all
+    idx = np.arange(n) if n <= m else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    d_idx = torch.from_numpy(idx).to(status.device)
+
+    def save(name, a):
+        np.save(os.path.join(path, pre + name + ".npy"), a)
+
+    save("sample_index", idx.astype(np.float64))
+    sums = []
+    for f, c in enumerate(cols):
+        save(f"col{f:02d}", c.index_select(0, d_idx).cpu().numpy().astype(np.float32))
+        sums.append(c.sum(0, dtype=torch.float64).reshape(-1))
+    save("status", status.index_select(0, d_idx).cpu().numpy().astype(np.float32))
+    sums.append(status.sum(dtype=torch.float64).reshape(1))
+    save("column_sums", torch.cat(sums).cpu().numpy())
 
 
 def kernel_time_events(fn, reps, lead=None, spread=False):
@@ -1061,6 +1098,36 @@ def run(args, env):
     total_records = sum_over_ranks(dist, float(n)) * args.steps
     value = total_records / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:  # the timed path's own output buffers, before anything else launches
+        dump_outputs(args.dump_outputs, out_cols, status, rank, world)
+    head = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "Mmsg/s",
+        "n_gpus": devices,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": "flat16-decode", "records_per_gpu": n,
+                   "mean_record_bytes": round(mean_rec, 1), "stream_bytes_per_gpu": stream_bytes,
+                   "parallelism": f"record-sharded x{world}, no collective",
+                   "ranks": world, "distinct_devices": devices,
+                   "rehearsal": devices < world,
+                   "backend": args.backend if world > 1 else None, "env": env},
+        "gb_s": round(total_records * (mean_rec + 8 + COLUMN_BYTES + 1) / elapsed / 1e9, 1),
+    }
+    if not args.full:  # a plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(head), file=_RESULT_OUT or sys.stdout, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # per-launch kernel time on the launch stream (HIP events)
     avg_ms, med_ms, p10_ms, p90_ms = kernel_time_events(dec, max(20, args.steps), spread=True)
@@ -1195,25 +1262,7 @@ def run(args, env):
 
     if rank == 0:
         line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "Mmsg/s",
-            "n_gpus": devices,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {"workload": "flat16-decode", "records_per_gpu": n,
-                       "mean_record_bytes": round(mean_rec, 1), "stream_bytes_per_gpu": stream_bytes,
-                       "parallelism": f"record-sharded x{world}, no collective",
-                       "ranks": world, "distinct_devices": devices,
-                       "rehearsal": devices < world,
-                       "backend": args.backend if world > 1 else None, "env": env},
-            "gb_s": round(total_records * (mean_rec + 8 + COLUMN_BYTES + 1) / elapsed / 1e9, 1),
+            **head,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "kernel": kname, "kernel_ms_avg": round(avg_ms, 5),

@@ -75,16 +75,13 @@ def test_unsupported_kinds():
 
 # ---- the full language (internal/lang/parser/grammar.y) and the reference's own schemas ----
 
-import glob  # noqa: E402
 import json  # noqa: E402
 import os  # noqa: E402
 
 from spec_amd import ListOf, Message, Struct  # noqa: E402
 from spec_amd.specfile import SpecFile, load_files  # noqa: E402
 
-REF = "/root/reference"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spec_trees.json")
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent (GPU box)")
 
 GRAMMAR = """
 import (
@@ -132,30 +129,6 @@ def test_grammar_constructs():
     assert methods["m6"][4] == {"in": "[]In"} and methods["sub"][2] == "Sub"
     assert methods["m1"][2] == [("a", "int64", 1), ("b", "float64", 2)]
     assert f.services["Sub"][0][0] == "hello"
-
-
-@needs_ref
-def test_every_reference_spec_parses():
-    files = sorted(glob.glob(REF + "/**/*.spec", recursive=True))
-    assert len(files) >= 9
-    for p in files:
-        f = SpecFile(open(p).read())
-        assert f.messages or f.enums or f.structs or f.services, p
-    svc = SpecFile(open(REF + "/internal/tests/pkg4/service.spec").read())
-    assert len(svc.services["Service"]) == 13 and len(svc.services["Subservice"]) == 1
-
-
-@needs_ref
-def test_reference_trees_match_fixture():
-    """The committed fixture (tests/golden/make_spec_trees.py) is what the parser derives today."""
-    import sys
-
-    sys.path.insert(0, os.path.dirname(GOLDEN))
-    from make_spec_trees import trees
-
-    want = json.load(open(GOLDEN))
-    got = trees(REF)
-    assert {k: [list(x) for x in v] for k, v in got.items()} == want
 
 
 def test_fixture_trees_shapes():

@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --no-cpu --no-extras > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -n 20 $OUT/bench_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu --no-extras > $OUT/bench_$i.json 2> $OUT/bench_$i.err || { tail -n 20 $OUT/bench_$i.err; exit 1; }
   python3 -c "import json,sys; d=json.load(open('$OUT/bench_$i.json')); r=d['roofline']; print('bench', $i, d['value'], d['ms_per_step'], r['kernel_ms_avg'], r['kernel_ms_median'], r['frac'])"
 done
 if [ $# -gt 0 ]; then

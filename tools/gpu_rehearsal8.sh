@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 t0=$(date +%s.%N)
-timeout -k 10 800 python bench.py --gpus 8 --backend gloo "$@" > $OUT/bench_gpus8_gloo.json 2> $OUT/err.log
+timeout -k 10 800 python bench.py --full --gpus 8 --backend gloo "$@" > $OUT/bench_gpus8_gloo.json 2> $OUT/err.log
 rc=$?
 t1=$(date +%s.%N)
 python3 -c "print('wall_s', round($t1 - $t0, 1))" | tee $OUT/wall.txt

@@ -21,11 +21,11 @@ if [ "$MODE" != quick ]; then
   python3 tools/pmc_traffic.py $OUT/pmc 1048576 $OUT/pmc_traffic.json > /dev/null && cp $OUT/pmc_traffic.json profiles/pmc_traffic.json && cat $OUT/pmc_traffic.json | head -n 12
 fi
 echo "== bench"
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -n 20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -n 20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 [ "$MODE" = quick ] && exit 0
 echo "== rocprofv3 stats + trace"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu > $OUT/prof.log 2>&1 || { tail -n 20 $OUT/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu > $OUT/prof.log 2>&1 || { tail -n 20 $OUT/prof.log; exit 1; }
 find $OUT/prof -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats.csv \;
 cut -d, -f1-4 $OUT/kernel_stats.csv | head -n 14
 f=$(find $OUT/prof -name '*kernel_trace.csv' | head -n 1)

@@ -12,5 +12,5 @@ timeout -k 10 300 python tools/bench_tree.py > $OUT/bench_tree.json 2> $OUT/benc
 cut -c1-600 $OUT/bench_tree.json
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -o run -- python3 tools/bench_tree.py > $OUT/prof.log 2>&1 || { tail -n 20 $OUT/prof.log; exit 1; }
 f=$(find $OUT/prof -name '*kernel_trace.csv' | head -n 1); python3 tools/tree_trace.py $f 1 | tee $OUT/tree_trace.txt
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -n 20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -n 20 $OUT/bench.err; exit 1; }
 cut -c1-400 $OUT/bench.json
