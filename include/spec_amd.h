@@ -475,10 +475,14 @@ int spec_frames_index_device(const uint8_t *buf, uint64_t len, uint64_t *ends, u
  * new connection): a later call continues with the frame's blocks.  *consumed = bytes the listed
  * blocks (and finished frames) span.  SPEC_E_CORRUPT on a bad header, SPEC_E_CAPACITY when more
  * than cap blocks are complete.  When a frame that carries a content checksum ends in the call
- * (its end mark), state->flags bit 2 is set and state->content_checksum holds the stored
- * checksum: compare it with spec_lz4_content_digest over the frame's decompressed bytes (what
- * lz4.Reader checks at the frame's end, pierrec/lz4/v4 frame.go; mpx writes it when a connection
- * closes).
+ * (its end mark), state->flags bit 2 is set, state->content_checksum holds the stored checksum
+ * and THE CALL STOPS THERE: *consumed ends just past that checksum, and every block the call
+ * listed belongs to that frame (or to frames before it that carry no content checksum), so the
+ * checksum is compared with spec_lz4_content_digest over the decompressed bytes of the frame's
+ * blocks, those of earlier calls included (what lz4.Reader checks at the frame's end,
+ * pierrec/lz4/v4 frame.go; mpx writes it when a connection closes).  Call again with
+ * buf + *consumed for the frames that follow.  Frames without a content checksum and skippable
+ * frames do not stop the call.
  * spec_lz4_decompress (DEVICE): block k (src[blocks[k].src_off, +src_len)) decompressed into
  * slots + k * slot_bytes (slot_bytes >= the block max size, a multiple of 16; slots 16-byte aligned); sizes[k] = its size, or
  * all-ones and status[k] = 1 for a corrupt block (pierrec decodeBlock's errors).

@@ -107,7 +107,9 @@ int spec_lz4_frame_blocks(const uint8_t *buf, uint64_t len, spec_lz4_state *stat
                 p += tail;
                 *consumed = p;
                 state->in_frame = 0;
-                more = true;
+                // a reported checksum ends the call: the blocks listed, consumed and the checksum
+                // all belong to this frame (the caller comes back with the rest of the buffer)
+                more = !ccs;
                 break;
             }
             const uint64_t sz = w & 0x7FFFFFFFu;

@@ -60,7 +60,11 @@ class ContentChecksum:
 
 def frame_blocks(buf: np.ndarray, state: Lz4State | None = None, cap: int | None = None):
     """-> (blocks: structured array [src_off, src_len, stored], consumed, block_max, rc).
-    rc is 0, or SPEC_E_CORRUPT (-6) / SPEC_E_CAPACITY (-4) with the blocks listed before it."""
+    rc is 0, or SPEC_E_CORRUPT (-6) / SPEC_E_CAPACITY (-4) with the blocks listed before it.
+    The call stops right after the end mark of a frame that carries a content checksum (state.flags
+    bit 2, state.content_checksum): consumed, the blocks and the checksum then belong to that
+    frame; call again with buf[consumed:] for what follows.  Frames without a content checksum and
+    skippable frames continue within the call."""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
     state = state if state is not None else Lz4State()
     cap = cap if cap is not None else buf.size // 4 + 1
