@@ -911,12 +911,84 @@ __device__ __forceinline__ bool fast_wide(const LdsSrc &s, int rs, int re, uint6
 
 // ---- kernel body -------------------------------------------------------------------------
 
-// One wave's group of 64 consecutive records: per-lane record bounds and the wave's span.
+// ---- staging a span of the stream into LDS -------------------------------------------------
+// One primitive for every kernel that parses from LDS (flat, nested, validate, tree rows): a
+// wave-uniform span of the stream is copied into a slab with LDS-DMA (buffer_load_dwordx4 ... lds:
+// 16 bytes per lane, 1 KiB per instruction, range-checked by the buffer descriptor), by one wave or
+// by the P waves of a group, which take the 1 KiB chunks round-robin.
+//   * origin: the span start rounded down to 16 bytes of the stream offset;
+//   * extent: whole 1 KiB chunks (what they hold past the span is never looked at);
+//   * AUX: the cache policy of the loads (the builtin's aux operand: 0 default, 2 = nt);
+//   * the 16-byte granule straddling the stream end comes back zeroed (whole-access range check)
+//     and is refilled bytewise by the wave that issued it.
+// Measured and not kept (DESIGN.md 3.1 "request shape"): nt on the stream, an origin on a 128-byte
+// line of the address, a last chunk with its upper lanes masked.
+constexpr int STREAM_AUX = 0;
+
+struct Staged {
+    uint64_t origin;   // stream offset of the slab's first staged byte (a multiple of 16)
+    uint32_t granules; // 16-byte granules covering the span: stream bytes [origin, origin + 16 granules)
+    __device__ __forceinline__ uint32_t chunks() const { return (granules + 63) >> 6; }
+    // LDS bytes the staging writes (whole chunks)
+    __device__ __forceinline__ uint32_t bytes() const { return chunks() * 1024; }
+};
+
+// The staging of stream bytes [lo, hi) (wave-uniform; hi <= lo stages nothing).
+__device__ __forceinline__ Staged stage_plan(uint64_t lo, uint64_t hi) {
+    Staged st;
+    st.origin = lo & ~15ull;
+    st.granules = hi > st.origin ? (uint32_t)((hi - st.origin + 15) >> 4) : 0;
+    return st;
+}
+
+// Wave `part` of `parts` issues its chunks of st into dst (16-byte aligned LDS, room for
+// st.bytes()); nothing is waited for.
+template <int AUX>
+__device__ __forceinline__ void stage_issue(__amdgpu_buffer_rsrc_t rsrc, uint8_t *dst, const Staged &st, int lane,
+                                            int part = 0, int parts = 1) {
+    // (wave-uniform values the compiler cannot prove uniform: a scalar loop, the LDS address in M0)
+    const uint32_t n = __builtin_amdgcn_readfirstlane(st.chunks());
+    for (uint32_t c = __builtin_amdgcn_readfirstlane((uint32_t)part); c < n; c += (uint32_t)parts)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(dst + c * 1024), 16,
+                                                 (uint32_t)st.origin + c * 1024 + lane * 16, 0, 0, AUX);
+}
+
+// Once the wave's own loads have landed (s_waitcnt vmcnt(0)): the one refill of the granule that
+// straddles stream_len, by the wave that issued it.  The wave's later LDS reads see it; other
+// waves of the group after their barrier.
+__device__ __forceinline__ void stage_fix_tail(__amdgpu_buffer_rsrc_t rsrc, uint8_t *dst, const Staged &st,
+                                               uint64_t stream_len, int lane, int part = 0, int parts = 1) {
+    const uint64_t tail = stream_len & ~15ull; // (origin is a multiple of 16: granules start on multiples of 16)
+    if (tail < stream_len && tail >= st.origin && tail < st.origin + st.bytes() &&
+        (int)(((tail - st.origin) >> 10) % (uint32_t)parts) == part) {
+        if (lane < 16 && tail + lane < stream_len)
+            dst[(tail - st.origin) + lane] = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// Issue, wait, refill: st's bytes are in dst when this returns (for a group of waves: this wave's
+// chunks; the slab is whole after the group's barrier).
+template <int AUX>
+__device__ __forceinline__ void stage_span(__amdgpu_buffer_rsrc_t rsrc, uint8_t *dst, const Staged &st,
+                                           uint64_t stream_len, int lane, int part = 0, int parts = 1) {
+    stage_issue<AUX>(rsrc, dst, st, lane, part, parts);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stage_fix_tail(rsrc, dst, st, stream_len, lane, part, parts);
+}
+
+// One wave's group of 64 consecutive records: per-lane record bounds and the wave's span, staged
+// (if it fits) at slab + SLAB_GUARD.
 struct Group {
     uint64_t rec_lo, rec_hi; // this lane's record [rec_lo, rec_hi) in the stream
-    uint64_t aligned_lo;     // span start rounded down to 16 (wave-uniform)
-    uint32_t chunks;         // 1 KiB DMA chunks covering the span (wave-uniform)
+    Staged st;               // the span's staging (wave-uniform)
     bool in_lds;             // span fits the slab (wave-uniform)
+    // the lane's record in slab positions, and slab position -> stream offset
+    __device__ __forceinline__ int rs() const { return SLAB_GUARD + (int)(rec_lo - st.origin); }
+    __device__ __forceinline__ int re() const { return SLAB_GUARD + (int)(rec_hi - st.origin); }
+    __device__ __forceinline__ long long to_stream() const { return (long long)st.origin - SLAB_GUARD; }
 };
 
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
@@ -933,44 +1005,24 @@ __device__ __forceinline__ void load_group_ends(const DecodeArgs &a, uint64_t ba
     lo = (r == 0 ? 0 : a.ends[(r - 1) < last ? r - 1 : last]) + a.head;
 }
 
-__device__ __forceinline__ Group make_group(const DecodeArgs &a, uint64_t base, int lane, uint64_t lo, uint64_t hi,
-                                            uint32_t slab) {
+// The group of lanes [l0, l1) of the 64 records from `base` (the whole group: 0, 64).  The slab
+// keeps 16 bytes past the staged chunks: a parser reads up to 7 bytes past a record end.
+__device__ __forceinline__ Group make_group(uint64_t n, uint64_t base, uint64_t lo, uint64_t hi, uint32_t slab,
+                                            int l0 = 0, int l1 = 64) {
     Group gr;
     gr.rec_lo = lo;
     gr.rec_hi = hi < lo ? lo : hi; // malformed ends: treat as empty
-    const uint64_t nrec = a.n - base < 64 ? a.n - base : 64;
-    const uint64_t span_lo = uniform64(__shfl(lo, 0));
-    const uint64_t span_hi = uniform64(__shfl(hi, (int)nrec - 1));
-    gr.aligned_lo = span_lo & ~15ull;
-    const uint64_t bytes = span_hi > gr.aligned_lo ? span_hi - gr.aligned_lo : 0;
-    const uint64_t chunks = (bytes + 1023) >> 10;
-    gr.chunks = (uint32_t)chunks;
-    gr.in_lds = slab > 0 && span_hi >= span_lo && SLAB_GUARD + chunks * 1024 + 16 <= (uint64_t)slab;
+    const int nrec = (int)(n - base < 64 ? n - base : 64);
+    const int last = (l1 < nrec ? l1 : nrec) - 1;
+    const uint64_t span_lo = uniform64(__shfl(lo, l0));
+    const uint64_t span_hi = uniform64(__shfl(hi, last < 0 ? 0 : last));
+    gr.st = stage_plan(span_lo, span_hi);
+    gr.in_lds = slab > 0 && l0 <= last && span_hi >= span_lo && SLAB_GUARD + (uint64_t)gr.st.bytes() + 16 <= (uint64_t)slab;
     return gr;
 }
-
-__device__ __forceinline__ void issue_dma(__amdgpu_buffer_rsrc_t rsrc, uint8_t *slab, const Group &gr, int lane) {
-    for (uint32_t c = 0; c < gr.chunks; c++) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc, (__attribute__((address_space(3))) void *)(slab + SLAB_GUARD + c * 1024), 16,
-            (uint32_t)gr.aligned_lo + c * 1024 + lane * 16, 0, 0, 0);
-    }
-}
-
-// The DMA'd 16-byte chunk holding the stream's last bytes came back zeroed if it straddles
-// the end (whole-access range check): refill it bytewise.
-__device__ __forceinline__ void fix_stream_tail(const DecodeArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint8_t *slab,
-                                                const Group &gr, int lane) {
-    const uint64_t tail = a.stream_len & ~15ull;
-    const uint64_t span_end = gr.aligned_lo + (uint64_t)gr.chunks * 1024;
-    if (tail < a.stream_len && tail >= gr.aligned_lo && tail < span_end) {
-        if (lane < 16 && tail + lane < a.stream_len)
-            slab[SLAB_GUARD + (tail - gr.aligned_lo) + lane] =
-                (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+__device__ __forceinline__ Group make_group(const DecodeArgs &a, uint64_t base, int lane, uint64_t lo, uint64_t hi,
+                                            uint32_t slab) {
+    return make_group(a.n, base, lo, hi, slab);
 }
 
 // Persistent waves: wave w of the grid decodes groups w, w + W, w + 2W, ... (W = waves in the
@@ -995,7 +1047,7 @@ __device__ __forceinline__ void decode_flat_body(const DecodeArgs &a) {
     uint64_t lo, hi;
     load_group_ends(a, a.r0 + g * 64, lane, lo, hi);
     Group cur = make_group(a, a.r0 + g * 64, lane, lo, hi, a.slab);
-    if (cur.in_lds) issue_dma(rsrc, slab, cur, lane);
+    if (cur.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, cur.st, lane);
     // the next group's ends are always one iteration ahead
     uint64_t gn = g + stride, nlo = 0, nhi = 0;
     if (gn < ngroups) load_group_ends(a, a.r0 + gn * 64, lane, nlo, nhi);
@@ -1011,27 +1063,26 @@ __device__ __forceinline__ void decode_flat_body(const DecodeArgs &a) {
         uint64_t lo2 = 0, hi2 = 0;
 
         if (cur.in_lds) {
-            fix_stream_tail(a, rsrc, slab, cur, lane);
+            stage_fix_tail(rsrc, slab + SLAB_GUARD, cur.st, a.stream_len, lane);
             LdsSrc s{(lds_u8 *)slab};
-            const int rs = SLAB_GUARD + (int)(cur.rec_lo - cur.aligned_lo);
-            const int re = SLAB_GUARD + (int)(cur.rec_hi - cur.aligned_lo);
-            const long long to_stream = (long long)cur.aligned_lo - SLAB_GUARD;
+            const int rs = cur.rs(), re = cur.re();
+            const long long to_stream = cur.to_stream();
             if constexpr (Spec::N > 0) {
                 FastRec<Spec> fr;
                 bool fast = valid && fast_prepare<Spec>(s, rs, re, fr);
                 if (valid && !fast) decode_record_generic(s, rs, re, r, a.f, to_stream);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // every LDS read of this group done
-                if (has_next && nxt.in_lds) issue_dma(rsrc, slab, nxt, lane);
+                if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
                 if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
                 if (fast) fast_finish<Spec, ERR>(fr, r, a.f, to_stream);
             } else {
                 if (valid) decode_record_generic(s, rs, re, r, a.f, to_stream);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (has_next && nxt.in_lds) issue_dma(rsrc, slab, nxt, lane);
+                if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
                 if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
             }
         } else {
-            if (has_next && nxt.in_lds) issue_dma(rsrc, slab, nxt, lane);
+            if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
             if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
             if (valid) {
                 GlobalSrc s{a.stream, a.stream_len};
@@ -1076,14 +1127,11 @@ __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
     lo += a.head;
     const Group cur = make_group(a, base, lane, lo, hi, a.slab);
     if (cur.in_lds) {
-        issue_dma(rsrc, slab, cur, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        fix_stream_tail(a, rsrc, slab, cur, lane);
+        stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, cur.st, a.stream_len, lane);
         if (!valid) return;
         LdsSrc s{(lds_u8 *)slab};
-        const int rs = SLAB_GUARD + (int)(cur.rec_lo - cur.aligned_lo);
-        const int re = SLAB_GUARD + (int)(cur.rec_hi - cur.aligned_lo);
-        const long long to_stream = (long long)cur.aligned_lo - SLAB_GUARD;
+        const int rs = cur.rs(), re = cur.re();
+        const long long to_stream = cur.to_stream();
         if constexpr (Spec::N > 0) {
             if constexpr (Spec::N <= FAST_MAX_FIELDS && !Spec::big) {
                 FastRec<Spec> fr;
@@ -1138,20 +1186,11 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
         }
         return;
     }
-    for (uint32_t c = (uint32_t)wave; c < cur.chunks; c += P)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(slab + SLAB_GUARD + c * 1024),
-                                                 16, (uint32_t)cur.aligned_lo + c * 1024 + lane * 16, 0, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // the chunk straddling the stream end is refilled by the wave that loaded it
-    const uint64_t tail = a.stream_len & ~15ull;
-    if (tail < a.stream_len && tail >= cur.aligned_lo && tail < cur.aligned_lo + (uint64_t)cur.chunks * 1024 &&
-        (int)(((tail - cur.aligned_lo) >> 10) % P) == wave && lane < 16 && tail + lane < a.stream_len)
-        slab[SLAB_GUARD + (tail - cur.aligned_lo) + lane] = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
+    stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, cur.st, a.stream_len, lane, wave, P);
     __syncthreads(); // the slab is whole
     LdsSrc s{(lds_u8 *)slab};
-    const int rs = SLAB_GUARD + (int)(cur.rec_lo - cur.aligned_lo);
-    const int re = SLAB_GUARD + (int)(cur.rec_hi - cur.aligned_lo);
-    const long long to_stream = (long long)cur.aligned_lo - SLAB_GUARD;
+    const int rs = cur.rs(), re = cur.re();
+    const long long to_stream = cur.to_stream();
     uint64_t errs = 0;
     const bool ok = valid && fast_wide_half<Spec, ERR, P>(s, rs, re, r, a.f, to_stream, wave, errs);
     // waves 1 .. P-1: verdicts at slab + 256 (w - 1), ERR: mask bits after them (512 B per wave)

@@ -106,11 +106,7 @@ __device__ __forceinline__ Group nested_stage(const NestedArgs &a, __amdgpu_buff
     d.head = 0;
     load_group_ends(d, base, lane, lo, hi);
     Group gr = make_group(d, base, lane, lo, hi, a.slab);
-    if (gr.in_lds) {
-        issue_dma(rsrc, slab, gr, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        fix_stream_tail(d, rsrc, slab, gr, lane);
-    }
+    if (gr.in_lds) stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
     return gr;
 }
 
@@ -127,22 +123,8 @@ __device__ __forceinline__ Group nested_stage_part(const NestedArgs &a, __amdgpu
     d.r0 = 0;
     d.head = 0;
     load_group_ends(d, base, lane, lo, hi);
-    Group gr;
-    gr.rec_lo = lo;
-    gr.rec_hi = hi < lo ? lo : hi;
-    const int nrec = (int)(a.n - base < 64 ? a.n - base : 64);
-    const int last = (l1 < nrec ? l1 : nrec) - 1;
-    const uint64_t span_lo = uniform64(__shfl(lo, l0));
-    const uint64_t span_hi = uniform64(__shfl(hi, last));
-    gr.aligned_lo = span_lo & ~15ull;
-    const uint64_t bytes = span_hi > gr.aligned_lo ? span_hi - gr.aligned_lo : 0;
-    gr.chunks = (uint32_t)((bytes + 1023) >> 10);
-    gr.in_lds = a.slab > 0 && l0 <= last && span_hi >= span_lo && SLAB_GUARD + (uint64_t)gr.chunks * 1024 + 16 <= a.slab;
-    if (gr.in_lds) {
-        issue_dma(rsrc, slab, gr, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        fix_stream_tail(d, rsrc, slab, gr, lane);
-    }
+    Group gr = make_group(a.n, base, lo, hi, a.slab, l0, l1);
+    if (gr.in_lds) stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
     return gr;
 }
 
@@ -467,9 +449,8 @@ __device__ __forceinline__ uint32_t nested_decode_part(const NestedArgs &a, __am
     const bool valid = r < a.n && lane >= l0 && lane < l1;
     if (gr.in_lds) {
         LdsSrc s{(lds_u8 *)slab};
-        return nested_group_body<OSpec, ISpec, false, U>(s, SLAB_GUARD + (long long)(gr.rec_lo - gr.aligned_lo),
-                                                      SLAB_GUARD + (long long)(gr.rec_hi - gr.aligned_lo), valid, r,
-                                                      g, item_base, lane, (long long)gr.aligned_lo - SLAB_GUARD, a,
+        return nested_group_body<OSpec, ISpec, false, U>(s, gr.rs(), gr.re(), valid, r, g, item_base, lane,
+                                                      gr.to_stream(), a,
                                                       RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
     }
     GlobalSrc s{a.stream, a.stream_len};
@@ -519,10 +500,9 @@ __device__ __forceinline__ void nested_decode_body(const NestedArgs &a) {
         const uint64_t r = base + lane;
         if (whole.in_lds) {
             LdsSrc s{(lds_u8 *)slab};
-            nested_group_body<OSpec, ISpec, false, U>(s, SLAB_GUARD + (long long)(whole.rec_lo - whole.aligned_lo),
-                                                   SLAB_GUARD + (long long)(whole.rec_hi - whole.aligned_lo),
+            nested_group_body<OSpec, ISpec, false, U>(s, whole.rs(), whole.re(),
                                                    r < a.n, r, g, item_base, lane,
-                                                   (long long)whole.aligned_lo - SLAB_GUARD, a,
+                                                   whole.to_stream(), a,
                                                    RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
             return;
         }
@@ -538,9 +518,8 @@ __device__ __forceinline__ void nested_decode_body(const NestedArgs &a) {
     const uint64_t item_base = 0;
     if (gr.in_lds) {
         LdsSrc s{(lds_u8 *)slab};
-        nested_group_body<OSpec, ISpec, ONEPASS>(s, SLAB_GUARD + (long long)(gr.rec_lo - gr.aligned_lo),
-                                                 SLAB_GUARD + (long long)(gr.rec_hi - gr.aligned_lo), valid, r, g,
-                                                 item_base, lane, (long long)gr.aligned_lo - SLAB_GUARD, a,
+        nested_group_body<OSpec, ISpec, ONEPASS>(s, gr.rs(), gr.re(), valid, r, g, item_base, lane,
+                                                 gr.to_stream(), a,
                                                  RANGES ? (uint32_t *)(slab + a.slab) : nullptr, xch);
     } else {
         GlobalSrc s{a.stream, a.stream_len};
@@ -605,21 +584,14 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
         }
         return;
     }
-    for (uint32_t c = (uint32_t)wave; c < gr.chunks; c += P)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(slab + SLAB_GUARD + c * 1024),
-                                                 16, (uint32_t)gr.aligned_lo + c * 1024 + lane * 16, 0, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t tail = a.stream_len & ~15ull;
-    if (tail < a.stream_len && tail >= gr.aligned_lo && tail < gr.aligned_lo + (uint64_t)gr.chunks * 1024 &&
-        (int)(((tail - gr.aligned_lo) >> 10) % P) == wave && lane < 16 && tail + lane < a.stream_len)
-        slab[SLAB_GUARD + (tail - gr.aligned_lo) + lane] = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
+    stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane, wave, P);
     __syncthreads(); // the slab is whole
     LdsSrc s{(lds_u8 *)slab};
-    const long long to_stream = (long long)gr.aligned_lo - SLAB_GUARD;
+    const long long to_stream = gr.to_stream();
     const uint64_t r = base + lane;
     const bool valid = r < a.n;
     ListInfo li = {0, 0, 0, 0, false};
-    const int rs = SLAB_GUARD + (int)(gr.rec_lo - gr.aligned_lo), re = SLAB_GUARD + (int)(gr.rec_hi - gr.aligned_lo);
+    const int rs = gr.rs(), re = gr.re();
     if constexpr (SELF) {
         if (valid) {
             if (wave == 0) li = decode_outer<OSpec>(s, rs, re, r, to_stream, a);
@@ -691,8 +663,7 @@ __device__ __forceinline__ void nested_count_body(const NestedArgs &a) {
         if (valid) {
             if (h.in_lds) {
                 LdsSrc s{(lds_u8 *)slab};
-                cnt = record_count(s, SLAB_GUARD + (long long)(h.rec_lo - h.aligned_lo),
-                                   SLAB_GUARD + (long long)(h.rec_hi - h.aligned_lo), a);
+                cnt = record_count(s, h.rs(), h.re(), a);
             } else {
                 GlobalSrc s{a.stream, a.stream_len};
                 cnt = record_count(s, (long long)h.rec_lo, (long long)h.rec_hi, a);

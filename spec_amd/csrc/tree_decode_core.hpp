@@ -90,21 +90,14 @@ __device__ __forceinline__ void tree_rows(const TreeBufs &B, uint32_t x, uint64_
         slo = (long long)uniform64((uint64_t)slo);
         shi = (long long)uniform64((uint64_t)shi);
         len = (long long)uniform64((uint64_t)len);
-        const long long sb = (slo > GUARD ? slo - GUARD : 0) & ~15ll, se = (shi + 16 + 15) & ~15ll;
-        const bool span = slab_bytes && slo < shi && se - sb + 16 <= (long long)slab_bytes;
+        // the span with its guard below and the parser's reads past a row end (stage_span, decode_core.hpp)
+        const Staged st = stage_plan((uint64_t)(slo > GUARD ? slo - GUARD : 0), (uint64_t)shi + 16);
+        const long long sb = (long long)st.origin;
+        // (slab_bytes is a multiple of 1 KiB, tree_decode.hip group_shape: the whole chunks fit too)
+        const bool span = slab_bytes && slo < shi && (uint64_t)st.granules * 16 + 16 <= (uint64_t)slab_bytes;
         const bool lanes = !span && slab_bytes >= 64 * LANE_W && len + GUARD + 48 <= LANE_W;
         if (span) {
-            // the span: LDS-DMA, 1 KiB per instruction, all in flight at once
-            const uint32_t chunks = (uint32_t)((se - sb + 1023) >> 10);
-            for (uint32_t c = 0; c < chunks; c++)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(slab + c * 1024),
-                                                         16, (uint32_t)sb + c * 1024 + lane * 16, 0, 0, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // a 16-byte chunk straddling the stream end comes back zeroed: refill it bytewise
-            const uint64_t tail = B.stream_len & ~15ull;
-            if (tail < B.stream_len && (long long)tail >= sb && (long long)tail < sb + (long long)chunks * 1024 &&
-                lane < 16 && tail + lane < B.stream_len)
-                slab[tail - sb + lane] = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
+            stage_span<STREAM_AUX>(rsrc, slab, st, B.stream_len, lane);
         } else if (lanes) {
             // each row in its lane's window: its 16-byte chunks, all loads issued before the stores
             uint8_t *win = slab + lane * LANE_W;
@@ -179,20 +172,11 @@ __device__ __forceinline__ void tree_rows_pair(const TreeBufs &B, uint32_t x, ui
         }
         slo = (long long)uniform64((uint64_t)slo);
         shi = (long long)uniform64((uint64_t)shi);
-        const long long sb = (slo > GUARD ? slo - GUARD : 0) & ~15ll, se = (shi + 16 + 15) & ~15ll;
-        const bool span = slab_bytes && slo < shi && se - sb + 16 <= (long long)slab_bytes;
-        if (span) {
-            const uint32_t chunks = (uint32_t)((se - sb + 1023) >> 10);
-            for (uint32_t c = (uint32_t)wave; c < chunks; c += P)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(slab + c * 1024),
-                                                         16, (uint32_t)sb + c * 1024 + lane * 16, 0, 0, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            // the straddling chunk is refilled by the wave that loaded it (after its own DMA landed)
-            const uint64_t tail = B.stream_len & ~15ull;
-            if (tail < B.stream_len && (long long)tail >= sb && (long long)tail < sb + (long long)chunks * 1024 &&
-                (int)(((tail - sb) >> 10) % P) == wave && lane < 16 && tail + lane < B.stream_len)
-                slab[tail - sb + lane] = (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rsrc, (uint32_t)(tail + lane), 0, 0);
-        }
+        const Staged st = stage_plan((uint64_t)(slo > GUARD ? slo - GUARD : 0), (uint64_t)shi + 16);
+        const long long sb = (long long)st.origin;
+        // (slab_bytes is a multiple of 1 KiB, tree_decode.hip group_shape: the whole chunks fit too)
+        const bool span = slab_bytes && slo < shi && (uint64_t)st.granules * 16 + 16 <= (uint64_t)slab_bytes;
+        if (span) stage_span<STREAM_AUX>(rsrc, slab, st, B.stream_len, lane, wave, P);
         __syncthreads(); // the slab is whole; the previous rows' exchange has been read
         RowOut ro = {0, 0, 0};
         if (valid) {

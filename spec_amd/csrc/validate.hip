@@ -207,14 +207,11 @@ __global__ __launch_bounds__(256) void parse_kernel(DecodeArgs a, uint32_t *size
     const Group gr = make_group(a, base, lane, lo, hi, a.slab);
     uint32_t st = ST_OK, size = 0;
     if (gr.in_lds) {
-        issue_dma(rsrc, slab, gr, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        fix_stream_tail(a, rsrc, slab, gr, lane);
+        stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
         if (!valid) return;
         LdsSrc s{(lds_u8 *)slab};
         LocalStack stk;
-        st = parse_record(s, SLAB_GUARD + (long long)(gr.rec_lo - gr.aligned_lo),
-                          SLAB_GUARD + (long long)(gr.rec_hi - gr.aligned_lo), root, size, stk);
+        st = parse_record(s, gr.rs(), gr.re(), root, size, stk);
     } else {
         if (!valid) return;
         GlobalSrc s{a.stream, a.stream_len};
