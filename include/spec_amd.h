@@ -466,6 +466,17 @@ size_t spec_frames_index_device_workspace_size(uint64_t len);
 int spec_frames_index_device(const uint8_t *buf, uint64_t len, uint64_t *ends, uint64_t cap, uint64_t *count,
                              uint64_t *consumed, int32_t *status, void *workspace, size_t workspace_size,
                              void *stream);
+/* spec_frames_write (DEVICE): the writer's side (mpx/conn_writer.go:84-97) over a whole batch.
+ * Record k ([ends[k-1], ends[k]) of stream_bytes) becomes [u32 big-endian size][bytes] at offset
+ * ends[k-1] + 4k of `frames`; the output is stream_len + 4n bytes (frames_cap >= that, else
+ * SPEC_E_CAPACITY; >= 4 GiB is SPEC_E_TOO_LARGE).  frame_ends (device, may be NULL) receives
+ * frame_ends[k] = ends[k] + 4(k + 1): the ends spec_frames_index_device reports and
+ * spec_decode_frames takes.  Any byte alignment of stream_bytes and frames; nothing outside
+ * frames[0, stream_len + 4n) is touched.  Asynchronous, no host synchronisation; n == 0 is a
+ * no-op.  ends must be non-decreasing and end at or before stream_len (a group of 64 records
+ * where they are not writes nothing). */
+int spec_frames_write(const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends, uint64_t n,
+                      uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends, void *stream);
 
 /* ---- LZ4 (mpx connection compression: mpx/conn_writer.go:42-56, conn_reader.go:53-62) ----
  * mpx wraps a connection in ONE LZ4 frame of independent blocks (pierrec/lz4/v4, 256 KiB blocks).

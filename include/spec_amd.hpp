@@ -230,6 +230,26 @@ class MessageBatchWriter {
     std::vector<uint64_t> lens_;
 };
 
+// ---- the send side of an mpx connection (mpx/conn_writer.go) ----
+// Frames of a batch in HBM: `[u32 BE size][record]` back to back, ends[k] = end of frame k.
+struct Frames {
+    DeviceBuffer bytes, ends;
+    uint64_t len = 0, n = 0;
+};
+
+// connWriter.writeMessage over a whole batch (conn_writer.go:84-97).  Asynchronous.
+inline Frames WriteFrames(const Batch &b, Stream &s) {
+    Frames f;
+    f.len = b.len + 4 * b.n;
+    f.n = b.n;
+    f.bytes = DeviceBuffer(f.len + 1);
+    f.ends = DeviceBuffer(b.n * 8 + 8);
+    Check(spec_frames_write((const uint8_t *)b.stream.data(), b.len, (const uint64_t *)b.ends.data(), b.n,
+                            (uint8_t *)f.bytes.data(), f.len, (uint64_t *)f.ends.data(), s.get()),
+          "spec_frames_write");
+    return f;
+}
+
 // Pinned host memory (hipHostMalloc): what an mpx connection reads frames into.
 class PinnedBuffer {
   public:

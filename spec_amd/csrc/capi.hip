@@ -506,6 +506,18 @@ int spec_frames_index_device(const uint8_t *buf, uint64_t len, uint64_t *ends, u
     return SPEC_OK;
 }
 
+// mpx/conn_writer.go:84-97 over a whole batch: [u32 BE size][record] for every record
+int spec_frames_write(const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends, uint64_t n,
+                      uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends, void *stream) {
+    if (n == 0) return SPEC_OK;
+    if (!ends || !frames || (!stream_bytes && stream_len)) return SPEC_E_INVALID_ARGUMENT;
+    if (n >= (1ull << 30) || stream_len + 4 * n >= (1ull << 32)) return SPEC_E_TOO_LARGE;
+    if (frames_cap < stream_len + 4 * n) return SPEC_E_CAPACITY;
+    if (spec::launch_frames_write(stream_bytes, stream_len, ends, n, frames, frame_ends, (hipStream_t)stream))
+        return hip_rc(hipGetLastError());
+    return SPEC_OK;
+}
+
 int spec_parse_messages(const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends, uint64_t n,
                         uint32_t head, uint8_t *status, uint32_t *sizes, void *stream) {
     return spec_parse_batch(SPEC_PARSE_MESSAGE, stream_bytes, stream_len, ends, n, head, status, sizes, stream);

@@ -4,7 +4,8 @@ An mpx connection carries `[u32 big-endian size][message]` frames back to back. 
 receiver indexes the frame heads on the host while the bytes arrive (`frames_index`, a C
 loop in libspec_amd.so) and decodes the frames where they lie (`decode_frames`: each record
 starts 4 bytes after the previous frame's end) — no compaction pass over the received bytes.
-`make_frames` builds such a buffer from records (test / benchmark input).
+`make_frames` builds such a buffer from records (test / benchmark input); `write_frames` is the
+sender's side on the device (spec_frames_write): encoded records in, frames out.
 """
 from __future__ import annotations
 
@@ -67,6 +68,26 @@ def make_frames_device(stream: torch.Tensor, ends: torch.Tensor) -> torch.Tensor
     for b in range(4):
         out[hpos + b] = ((sizes >> (8 * (3 - b))) & 0xff).to(torch.uint8)
     return out
+
+
+def write_frames(stream: torch.Tensor, ends: torch.Tensor, *, out: torch.Tensor | None = None, cuda_stream=None):
+    """spec_frames_write: records (device stream + int64 ends) -> (frames uint8 device tensor of
+    stream.numel() + 4 n bytes, frame_ends int64 [n]) — `[u32 BE size][record]` back to back, what
+    mpx puts on the wire; frame_ends is what frames_index_device reports and decode_frames takes.
+    `out` (optional, uint8, at least that long, any byte alignment) receives the frames.
+    Asynchronous."""
+    _check_dev(stream, "stream", torch.uint8)
+    _check_dev(ends, "ends", torch.int64)
+    n, total = ends.numel(), stream.numel() + 4 * ends.numel()
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=stream.device)
+    else:
+        _check_dev(out, "out", torch.uint8)
+    frame_ends = torch.empty(n, dtype=torch.int64, device=stream.device)
+    rc = _lib.lib().spec_frames_write(_ptr(stream) if stream.numel() else None, stream.numel(), _ptr(ends), n,
+                                      _ptr(out), out.numel(), _ptr(frame_ends), _stream_handle(cuda_stream))
+    _lib.check(rc, "spec_frames_write")
+    return out[:total], frame_ends
 
 
 def make_frames(stream: np.ndarray, ends: np.ndarray) -> np.ndarray:
