@@ -685,6 +685,22 @@ int spec_encode_flat(const spec_schema *schema, const void *const *columns,
                      const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n,
                      uint8_t *out, uint64_t out_cap, uint64_t *ends, void *workspace,
                      size_t workspace_size, uint64_t *total, void *stream);
+/* spec_encode_flat_frames: spec_encode_flat with every record behind its mpx frame head
+ * (connWriter.writeMessage, mpx/conn_writer.go:84-97): record k becomes
+ * [u32 big-endian size_k][message_k], the frames back to back from frames[0] — exactly the bytes
+ * of spec_frames_write over spec_encode_flat's stream, from the encoder's own three launches (the
+ * head is emitted with the record; no unframed stream exists in between).  frame_ends[k] is the
+ * offset just past frame k = spec_encode_flat's ends[k] + 4(k + 1): the ends
+ * spec_frames_index_device reports and spec_decode_frames / spec_parse_messages(head = 4) take.
+ * *total (device uint64) = the framed size = spec_encode_flat_size's total + 4n, or all-ones on
+ * an encoder error; if it exceeds frames_cap nothing is written to frames/frame_ends.  Workspace,
+ * argument checks and return codes are spec_encode_flat's.  Asynchronous, no host
+ * synchronisation.  Any byte alignment of `frames`; nothing outside frames[0, *total) is written.
+ * Positions are 64-bit: no size limit beyond the encoder's. */
+int spec_encode_flat_frames(const spec_schema *schema, const void *const *columns,
+                            const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n,
+                            uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends,
+                            void *workspace, size_t workspace_size, uint64_t *total, void *stream);
 
 /* ---- nested encode (list<message>) ----
  * For every record i, what a generated Write() does (writer_list_msg.go:8-47): the outer

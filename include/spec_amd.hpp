@@ -180,6 +180,13 @@ inline DeviceBuffer ParseMessageBatch(const Batch &b, Stream &s, uint32_t head =
     return st;
 }
 
+// ---- the send side of an mpx connection (mpx/conn_writer.go) ----
+// Frames of a batch in HBM: `[u32 BE size][record]` back to back, ends[k] = end of frame k.
+struct Frames {
+    DeviceBuffer bytes, ends;
+    uint64_t len = 0, n = 0;
+};
+
 // For every record: w := NewMessageWriterBuffer(buf); w.Field(tag_f).<Kind_f>(column_f[i])...; w.Build().
 class MessageBatchWriter {
   public:
@@ -222,19 +229,41 @@ class MessageBatchWriter {
         return b;
     }
 
+    // Build() + WriteFrames() in the encoder's own launches (spec_encode_flat_frames): every record
+    // as connWriter.writeMessage sends it (conn_writer.go:84-97), no unframed stream in between.
+    Frames BuildFrames(Stream &s) {
+        spec_schema c = schema_.C();
+        const size_t ws = spec_encode_flat_workspace_size(n_);
+        DeviceBuffer work(ws), total(8);
+        Check(spec_encode_flat_size(&c, cols_.data(), n_, work.data(), ws, (uint64_t *)total.data(), s.get()),
+              "spec_encode_flat_size");
+        uint64_t t = 0;
+        total.CopyTo(&t, 8, s);
+        s.Sync();
+        if (t == ~0ull) throw Error(SPEC_E_INVALID_ARGUMENT, "MessageBatchWriter::BuildFrames (encoder error)");
+        Frames f;
+        f.len = t + 4 * n_;
+        f.n = n_;
+        f.bytes = DeviceBuffer(f.len + 1);
+        f.ends = DeviceBuffer(n_ * 8 + 8);
+        Check(spec_encode_flat_frames(&c, cols_.data(), heaps_.data(), lens_.data(), n_, (uint8_t *)f.bytes.data(),
+                                      f.len, (uint64_t *)f.ends.data(), work.data(), ws, (uint64_t *)total.data(),
+                                      s.get()),
+              "spec_encode_flat_frames");
+        uint64_t t2 = 0;
+        total.CopyTo(&t2, 8, s);
+        s.Sync();
+        if (t2 != f.len)
+            throw Error(SPEC_E_INVALID_ARGUMENT, "MessageBatchWriter::BuildFrames (span outside its heap)");
+        return f;
+    }
+
   private:
     Schema schema_;
     uint64_t n_;
     std::vector<const void *> cols_;
     std::vector<const uint8_t *> heaps_;
     std::vector<uint64_t> lens_;
-};
-
-// ---- the send side of an mpx connection (mpx/conn_writer.go) ----
-// Frames of a batch in HBM: `[u32 BE size][record]` back to back, ends[k] = end of frame k.
-struct Frames {
-    DeviceBuffer bytes, ends;
-    uint64_t len = 0, n = 0;
 };
 
 // connWriter.writeMessage over a whole batch (conn_writer.go:84-97).  Asynchronous.

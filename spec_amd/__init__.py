@@ -7,7 +7,7 @@ decoded into SoA columns / encoded from them by hand-written gfx950 kernels
 """
 from ._lib import LIB_PATH, SpecError, header_symbols, lib, set_jit
 from .batch import (PARSE_LIST, PARSE_MESSAGE, PARSE_VALUE, Columns, Decoder, Encoder, alloc_columns, decode_flat,
-                    decode_flat_errors, encode_flat, parse_messages)
+                    decode_flat_errors, encode_flat, encode_flat_frames, parse_messages)
 from . import lz4
 from .frames import decode_frames, frames_index, frames_index_device, make_frames, make_frames_device, write_frames
 from .pipeline import HostDecoder
@@ -18,7 +18,7 @@ from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, Tree
 
 __all__ = [
     "HostDecoder", "decode_frames", "frames_index", "frames_index_device", "make_frames", "make_frames_device", "write_frames", "LIB_PATH", "SpecError", "header_symbols", "lib", "set_jit", "Columns", "Decoder", "Encoder", "alloc_columns",
-    "decode_flat", "decode_flat_errors", "encode_flat", "parse_messages", "PARSE_MESSAGE", "PARSE_LIST", "PARSE_VALUE",
+    "decode_flat", "decode_flat_errors", "encode_flat", "encode_flat_frames", "parse_messages", "PARSE_MESSAGE", "PARSE_LIST", "PARSE_VALUE",
     "FLAT16", "Field", "Kind", "Schema",
     "NESTED", "NestedSchema", "NestedColumns", "NestedDecoder", "NestedEncoder", "decode_nested",
     "encode_nested", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",

@@ -153,6 +153,20 @@ class Encoder:
                 raise ValueError(f"column {i} too small")
         return (C.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
 
+    def _heapptrs(self, heaps):
+        nf = len(self.schema)
+        hp = (C.c_void_p * max(1, nf))()
+        hl = (C.c_uint64 * max(1, nf))()
+        keep = []
+        for f, fld in enumerate(self.schema.fields):
+            if fld.kind in VARLEN:
+                h = heaps[f]
+                _check_dev(h, f"heap {f}", torch.uint8)
+                keep.append(h)
+                hp[f] = h.data_ptr()
+                hl[f] = h.numel()
+        return hp, hl, keep
+
     def size(self, cols, cuda_stream=None) -> torch.Tensor:
         """Sizing passes only; returns the device total (int64[1])."""
         rc = _lib.lib().spec_encode_flat_size(C.byref(self.schema.c), self._colptrs(cols), self.n,
@@ -165,21 +179,22 @@ class Encoder:
         """All passes; writes out[:total], ends[n] and self.total (device)."""
         _check_dev(out, "out", torch.uint8)
         _check_dev(ends, "ends", torch.int64)
-        nf = len(self.schema)
-        hp = (C.c_void_p * max(1, nf))()
-        hl = (C.c_uint64 * max(1, nf))()
-        keep = []
-        for f, fld in enumerate(self.schema.fields):
-            if fld.kind in VARLEN:
-                h = heaps[f]
-                _check_dev(h, f"heap {f}", torch.uint8)
-                keep.append(h)
-                hp[f] = h.data_ptr()
-                hl[f] = h.numel()
+        hp, hl, _keep = self._heapptrs(heaps)
         rc = _lib.lib().spec_encode_flat(C.byref(self.schema.c), self._colptrs(cols), hp, hl, self.n,
                                          _ptr(out), out.numel(), _ptr(ends), _ptr(self.workspace),
                                          self.ws_bytes, _ptr(self.total), _stream_handle(cuda_stream))
         _lib.check(rc, "spec_encode_flat")
+
+    def encode_frames_into(self, cols, heaps: dict, out: torch.Tensor, ends: torch.Tensor, cuda_stream=None):
+        """spec_encode_flat_frames: all passes; writes the mpx frames `[u32 BE size][message]` to
+        out[:total], the frame ends to ends[n] and the framed size to self.total (device)."""
+        _check_dev(out, "out", torch.uint8)
+        _check_dev(ends, "ends", torch.int64)
+        hp, hl, _keep = self._heapptrs(heaps)
+        rc = _lib.lib().spec_encode_flat_frames(C.byref(self.schema.c), self._colptrs(cols), hp, hl, self.n,
+                                                _ptr(out), out.numel(), _ptr(ends), _ptr(self.workspace),
+                                                self.ws_bytes, _ptr(self.total), _stream_handle(cuda_stream))
+        _lib.check(rc, "spec_encode_flat_frames")
 
 
 def encode_flat(schema: Schema, cols, heaps: dict, n: int | None = None, cuda_stream=None):
@@ -196,6 +211,25 @@ def encode_flat(schema: Schema, cols, heaps: dict, n: int | None = None, cuda_st
     enc.encode_into(cols, heaps, out, ends, cuda_stream)
     if int(enc.total.item()) != total:  # heap-range check failed in the full pass
         raise _lib.SpecError(-1, "spec_encode_flat: encoder error (span outside its heap)")
+    return out[:total], ends
+
+
+def encode_flat_frames(schema: Schema, cols, heaps: dict, n: int | None = None, cuda_stream=None):
+    """Encode a batch straight to mpx frames -> (frames uint8[total + 4n], frame_ends int64[n]) on the
+    device: the bytes and ends of frames.write_frames(*encode_flat(...)), in the encoder's launches."""
+    if n is None:
+        n = cols[0].shape[0] if cols else 0
+    dev = cols[0].device if cols else torch.device("cuda")
+    enc = Encoder(schema, n, dev)
+    total = int(enc.size(cols, cuda_stream).item())
+    if total < 0:  # ~0: an encoder error (string/bytes span outside its heap or > MaxSize)
+        raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error")
+    total += 4 * n
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    ends = torch.empty(n, dtype=torch.int64, device=dev)
+    enc.encode_frames_into(cols, heaps, out, ends, cuda_stream)
+    if int(enc.total.item()) != total:  # heap-range check failed in the full pass
+        raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error (span outside its heap)")
     return out[:total], ends
 
 

@@ -248,7 +248,7 @@ void note_hip_error(hipError_t e) {
 int encode_flat_passes(const spec_schema *schema, const void *const *columns, const uint8_t *const *heaps,
                        const uint64_t *heap_lens, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *ends,
                        uint64_t ends_base, void *workspace, size_t workspace_size, uint64_t *total, int passes,
-                       hipStream_t stream) {
+                       hipStream_t stream, uint32_t frame_head) {
     int rc = check_schema(schema);
     if (rc) return rc;
     if (!columns || !workspace || (n && (!ends || !out))) return SPEC_E_INVALID_ARGUMENT;
@@ -261,6 +261,7 @@ int encode_flat_passes(const spec_schema *schema, const void *const *columns, co
         WideEncodeArgs w{};
         if ((rc = fill_wide_encode_args(w, schema, columns, heaps, heap_lens, n, workspace, stream))) return rc;
         w.check_heaps = 1;
+        w.frame_head = frame_head;
         w.out = out;
         w.out_cap = out_cap;
         w.ends = ends;
@@ -282,6 +283,7 @@ int encode_flat_passes(const spec_schema *schema, const void *const *columns, co
         }
     }
     a.check_heaps = 1;
+    a.frame_head = frame_head;
     a.out = out;
     a.out_cap = out_cap;
     a.ends = ends;
@@ -875,6 +877,17 @@ int spec_encode_flat(const spec_schema *schema, const void *const *columns,
     return spec::encode_flat_passes(schema, columns, heaps, heap_lens, n, out, out_cap, ends, 0, workspace,
                                     workspace_size, total, spec::ENC_PASS_SIZE | spec::ENC_PASS_WRITE,
                                     (hipStream_t)stream);
+}
+
+// spec_encode_flat with every record behind its mpx frame head (mpx/conn_writer.go:84-97): the
+// bytes of spec_frames_write over spec_encode_flat's stream, from the encoder's three launches
+int spec_encode_flat_frames(const spec_schema *schema, const void *const *columns,
+                            const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n,
+                            uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends, void *workspace,
+                            size_t workspace_size, uint64_t *total, void *stream) {
+    return spec::encode_flat_passes(schema, columns, heaps, heap_lens, n, frames, frames_cap, frame_ends, 0, workspace,
+                                    workspace_size, total, spec::ENC_PASS_SIZE | spec::ENC_PASS_WRITE,
+                                    (hipStream_t)stream, 4);
 }
 
 } // extern "C"

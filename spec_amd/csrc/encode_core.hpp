@@ -43,6 +43,7 @@ struct EncodeArgs {
     uint64_t n;
     EncFields f;
     uint32_t check_heaps;  // 1 when heaps/heap_lens are known (full encode, not size-only)
+    uint32_t frame_head;   // 0, or 4: every record behind its mpx frame head (selects the framed kernels)
     uint8_t *out;
     uint64_t out_cap;
     uint64_t *ends;
@@ -58,6 +59,7 @@ struct WideEncodeArgs {
     uint64_t n;
     WideEncFields f;
     uint32_t check_heaps;
+    uint32_t frame_head;
     uint8_t *out;
     uint64_t out_cap;
     uint64_t *ends;
@@ -157,7 +159,12 @@ __device__ __forceinline__ RecSize record_size(const FS &a, uint64_t r, bool che
 // sums: loaded coalesced (all loads in flight) into LDS, each thread scans 8 CONSECUTIVE sums
 // serially, one block scan of the thread sums per tile (a block scan costs ~1 us of barriers
 // and shuffles on the one CU), results back through LDS, coalesced stores.
-__device__ __forceinline__ void scan_block_sums(uint64_t *block_sums, uint64_t nblocks, uint64_t *total) {
+// HEAD (the framed encode, encode_write_body<P, A, HEAD>): every one of the n records grows by a
+// HEAD-byte frame head the size kernels did not count, so block k's sum gains HEAD x (its
+// records: ENC_BLOCK, fewer in the last block); an error sum stays all-ones.
+template <int HEAD = 0>
+__device__ __forceinline__ void scan_block_sums(uint64_t *block_sums, uint64_t nblocks, uint64_t *total,
+                                                uint64_t n = 0) {
     constexpr int PER = 8, TILE = 1024 * PER;
     __shared__ uint64_t tv[TILE + TILE / 16]; // +1 pad per 16: thread-contiguous reads spread banks
     __shared__ uint64_t wsum[16];
@@ -173,6 +180,12 @@ __device__ __forceinline__ void scan_block_sums(uint64_t *block_sums, uint64_t n
         for (int i = 0; i < PER; i++) {
             const uint64_t k = tile + (uint64_t)i * 1024 + t;
             v[i] = k < nblocks ? block_sums[k] : 0;
+            if constexpr (HEAD != 0) {
+                if (k < nblocks && v[i] != ~0ull) {
+                    const uint64_t left = n - k * ENC_BLOCK;
+                    v[i] += (uint64_t)HEAD * (left < (uint64_t)ENC_BLOCK ? left : (uint64_t)ENC_BLOCK);
+                }
+            }
         }
 #pragma unroll
         for (int i = 0; i < PER; i++) {
@@ -634,11 +647,19 @@ struct RuntimeEnc {
                                                    const Lists &lists = Lists()) {
         return record_size(f, r, check, err, lists);
     }
-    template <class Sink, class Pos, class Lists = NoListEmit, class FS, class Inv>
+    // HEAD = 4: the mpx frame head (u32 BE message size, mpx/conn_writer.go:84-97) at p, the
+    // message behind it; its table and trailer are placed from the message's first byte
+    template <int HEAD = 0, class Sink, class Pos, class Lists = NoListEmit, class FS, class Inv>
     static __device__ __forceinline__ void emit(const FS &f, const Sink &k, Pos p, uint64_t r, const Rec &,
                                                 const RecSize &rs, const Inv *inv_order,
                                                 const Lists &lists = Lists()) {
-        emit_message(f, k, p, r, rs, inv_order, lists);
+        if constexpr (HEAD != 0) {
+            static_assert(HEAD == 4, "the frame head is a u32");
+            Emit<Sink, Pos> hd(k, p);
+            hd.put4(bswap32((uint32_t)rs.total));
+            hd.finish();
+        }
+        emit_message(f, k, p + (Pos)HEAD, r, rs, inv_order, lists);
     }
 };
 
@@ -975,12 +996,20 @@ struct SpecEnc {
     // With a list field the emitter jumps over the list's items (written later by other lanes:
     // encode_nested_core.hpp phase B).  HEAD_ST4 stays valid: the first store after the jump may
     // clobber <= 3 bytes of the last item, which phase B then writes.
-    template <class Sink, class Pos, class Lists = NoListEmit>
-    static __device__ __forceinline__ void emit(const EncFields &f, const Sink &k, Pos start, uint64_t r,
+    // HEAD = 4: the mpx frame head (u32 BE message size) is the first append of the SAME emitter
+    // sequence, so the HEAD_ST4 first-dword store lies below the head, never over it; the field
+    // ends count from the message's first byte, `start`.
+    template <int HEAD = 0, class Sink, class Pos, class Lists = NoListEmit>
+    static __device__ __forceinline__ void emit(const EncFields &f, const Sink &k, Pos fstart, uint64_t r,
                                                 const Rec &rec, const RecSize &rs, const uint8_t *,
                                                 const Lists &lists = Lists()) {
         Rec x = rec;
-        Emit<Sink, Pos, Sink::kHeadSt4> em(k, start);
+        Emit<Sink, Pos, Sink::kHeadSt4> em(k, fstart);
+        if constexpr (HEAD != 0) {
+            static_assert(HEAD == 4, "the frame head is a u32");
+            em.put4(bswap32((uint32_t)rs.total));
+        }
+        const Pos start = fstart + (Pos)HEAD;
         emit_values<0>(f, em, x, start, r, lists);
         if constexpr (Sink::kHeadSt4 && !Spec::big_forced && RUN_M <= 18) {
             if (__ballot(rs.big) == 0) { // wave-uniform: every record of the wave has a small table
@@ -1056,7 +1085,11 @@ __device__ __forceinline__ void copy_slab_out(const uint8_t *slab, uint8_t *gbas
 // into the wave's LDS slab, the wave copies the slab to HBM with 16-byte stores; ends[]
 // written coalesced.  A wave whose output span does not fit the slab emits straight to HBM.
 // smem: ENC_LDS_HEAD bytes of header, then ENC_BLOCK / 64 slabs of ENC_SLAB bytes.
-template <class P, class A>
+// HEAD = 4 (spec_encode_flat_frames): every record is [u32 BE size][message]; the scanned size of
+// a record is its message's + HEAD, the block offsets and the total come from
+// scan_block_sums<HEAD>, ends[] are frame ends and [S, E) is the framed span.  HEAD = 0 is the
+// unframed encoder, instruction for instruction.
+template <class P, class A, int HEAD = 0>
 __device__ __forceinline__ void encode_write_body(const A &a, uint8_t *smem) {
     uint64_t *wsum = (uint64_t *)smem;
     // the table position of every field: built in LDS from the Writer's order, or (a wide
@@ -1079,7 +1112,8 @@ __device__ __forceinline__ void encode_write_body(const A &a, uint8_t *smem) {
     bool err = false;
     RecSize rs = P::size(a.f, rec, r, false, err);
     if (!valid) rs.total = 0;
-    uint64_t x = rs.total; // block exclusive scan of sizes
+    const uint64_t sz = rs.total + (valid ? HEAD : 0); // the record's bytes in the output
+    uint64_t x = sz; // block exclusive scan of sizes
     for (int o = 1; o < 64; o <<= 1) {
         const uint64_t y = __shfl_up(x, o);
         if (lane >= o) x += y;
@@ -1088,8 +1122,8 @@ __device__ __forceinline__ void encode_write_body(const A &a, uint8_t *smem) {
     lds_barrier(); // (heap loads still in flight)
     uint64_t pre = blk_pre;
     for (int w = 0; w < wave; w++) pre += wsum[w];
-    const uint64_t start = pre + x - rs.total;
-    if (valid) a.ends[r] = a.ends_base + start + rs.total;
+    const uint64_t start = pre + x - sz;
+    if (valid) a.ends[r] = a.ends_base + start + sz;
 
     // wave output span [S, E)
     const uint64_t wbase = (uint64_t)blockIdx.x * ENC_BLOCK + wave * 64;
@@ -1097,21 +1131,21 @@ __device__ __forceinline__ void encode_write_body(const A &a, uint8_t *smem) {
     const uint64_t S = __builtin_amdgcn_readfirstlane((uint32_t)start) |
                        ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(start >> 32)) << 32);
     const int last = (int)((a.n - wbase) < 64 ? a.n - wbase - 1 : 63);
-    const uint64_t Ev = __shfl(start + rs.total, last);
+    const uint64_t Ev = __shfl(start + sz, last);
     const uint64_t E = __builtin_amdgcn_readfirstlane((uint32_t)Ev) |
                        ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(Ev >> 32)) << 32);
     const uint64_t head = ((uint64_t)(a.out + S)) & 15; // slab pos of byte S keeps 16-B phase
     if (head + (E - S) + 16 <= (uint64_t)ENC_SLAB) {
         uint8_t *slab = smem + ENC_LDS_HEAD + wave * ENC_SLAB;
         LdsSink k{slab, (int)(smem + ENC_LDS_HEAD - 4 - slab)}; // dummy: last header dword (unused)
-        if (valid) P::emit(a.f, k, (int)(head + (start - S)), r, rec, rs, inv_order);
+        if (valid) P::template emit<HEAD>(a.f, k, (int)(head + (start - S)), r, rec, rs, inv_order);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         copy_slab_out(slab, a.out + S - head, head, head + (E - S), lane);
     } else if (valid) {
         GlobalSink k{a.out};
-        P::emit(a.f, k, (long long)start, r, rec, rs, inv_order);
+        P::template emit<HEAD>(a.f, k, (long long)start, r, rec, rs, inv_order);
     }
 }
 

@@ -23,6 +23,11 @@
 //                            not fit the slab emits straight to HBM.
 // Passes 1 and 3 are, for schemas jit.cpp accepts, schema-specialised kernels compiled at run
 // time (all column loads of a record issued together, the table emitted from registers).
+//
+// spec_encode_flat_frames (EncodeArgs::frame_head = 4) runs the same three launches with the
+// framed instantiations of passes 2 and 3: every record leaves as its mpx frame
+// [u32 BE size][message] (mpx/conn_writer.go:84-97), the head emitted into the slab with the
+// record.  Pass 1 is shared; pass 2 adds the heads to the block sums.
 #include <hip/hip_runtime.h>
 
 #include "../../include/spec_amd.h"
@@ -57,16 +62,42 @@ __global__ __launch_bounds__(ENC_BLOCK) void encode_wide_write_kernel(WideEncode
     encode_write_body<RuntimeEnc>(a, smem);
 }
 
+// The framed encoders: frame heads counted by the scan, written by the write pass.
+constexpr int FRAME_HEAD = 4;
+
+__global__ __launch_bounds__(1024) void encode_scan_frames_kernel(EncodeArgs a) {
+    scan_block_sums<FRAME_HEAD>(a.block_sums, a.nblocks, a.total, a.n);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_write_frames_kernel(EncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimeEnc, EncodeArgs, FRAME_HEAD>(a, smem);
+}
+
+__global__ __launch_bounds__(1024) void encode_wide_scan_frames_kernel(WideEncodeArgs a) {
+    scan_block_sums<FRAME_HEAD>(a.block_sums, a.nblocks, a.total, a.n);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_wide_write_frames_kernel(WideEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimeEnc, WideEncodeArgs, FRAME_HEAD>(a, smem);
+}
+
 int launch_encode_wide_size(const WideEncodeArgs &a, hipStream_t stream) {
     if (a.nblocks) hipLaunchKernelGGL(encode_wide_size_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), 0, stream, a);
-    hipLaunchKernelGGL(encode_wide_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+    if (a.frame_head) hipLaunchKernelGGL(encode_wide_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL(encode_wide_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_encode_wide_write(const WideEncodeArgs &a, hipStream_t stream) {
     if (!a.nblocks) return 0;
-    hipLaunchKernelGGL(encode_wide_write_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(),
-                       stream, a);
+    if (a.frame_head)
+        hipLaunchKernelGGL(encode_wide_write_frames_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK),
+                           enc_write_lds_bytes(), stream, a);
+    else
+        hipLaunchKernelGGL(encode_wide_write_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(),
+                           stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -74,7 +105,8 @@ int launch_encode_size(const spec_schema *schema, const EncodeArgs &a, hipStream
     int j = a.nblocks ? jit_launch_encode(schema, a, false, stream) : 1;
     if (j < 0) return -1;
     if (j == 0) hipLaunchKernelGGL(encode_size_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), 0, stream, a);
-    hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+    if (a.frame_head) hipLaunchKernelGGL(encode_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL(encode_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -82,7 +114,10 @@ int launch_encode_write(const spec_schema *schema, const EncodeArgs &a, hipStrea
     if (!a.nblocks) return 0;
     int j = jit_launch_encode(schema, a, true, stream);
     if (j < 0) return -1;
-    if (j == 0)
+    if (j == 0 && a.frame_head)
+        hipLaunchKernelGGL(encode_write_frames_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(),
+                           stream, a);
+    else if (j == 0)
         hipLaunchKernelGGL(encode_write_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(),
                            stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;

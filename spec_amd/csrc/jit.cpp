@@ -325,7 +325,12 @@ std::string generate_encode(const spec_schema *s) {
       << "  spec::encode_size_body<P>(a);\n}\n"
       << "extern \"C\" __global__ __launch_bounds__(256) void spec_encode_write_jit(spec::EncodeArgs a) {\n"
       << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
-      << "  spec::encode_write_body<P>(a, smem);\n}\n";
+      << "  spec::encode_write_body<P>(a, smem);\n}\n"
+      // spec_encode_flat_frames: the same write pass with the 4-byte mpx frame head per record,
+      // a second instantiation in the same module (the unframed kernel's code does not change)
+      << "extern \"C\" __global__ __launch_bounds__(256) void spec_encode_write_frames_jit(spec::EncodeArgs a) {\n"
+      << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
+      << "  spec::encode_write_body<P, spec::EncodeArgs, 4>(a, smem);\n}\n";
     if (const int h = enc_pair_split(s))
         o << "extern \"C\" __global__ __launch_bounds__(512) void spec_encode_write_pair_jit(spec::EncodeArgs a) {\n"
           << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
@@ -486,7 +491,8 @@ Entry load(const std::vector<char> &code, Prog p) {
     }
     const char *names[4][4] = {{"spec_decode_flat_jit", "spec_decode_flat_err_jit", "spec_decode_flat_pair_jit",
                                 "spec_decode_flat_err_pair_jit"},
-                               {"spec_encode_size_jit", "spec_encode_write_jit", nullptr, nullptr}, // (+ the pair kernel, optional)
+                               {"spec_encode_size_jit", "spec_encode_write_jit", nullptr, // ([2]: the pair kernel, optional)
+                                "spec_encode_write_frames_jit"},
                                {"spec_decode_nested_jit", "spec_decode_nested2_jit", "spec_decode_nested3_jit",
                                 "spec_decode_nested_pair_jit"},
                                {"spec_encode_nested_size_jit", "spec_encode_nested_write_jit", nullptr, nullptr}};
@@ -1892,7 +1898,10 @@ int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
     hipError_t rc;
-    if (write && e->fn[2]) { // the write pass on wave pairs (encode_write_pair_body)
+    if (write && a.frame_head) { // the framed write pass: never the pair kernel, which knows no head
+        rc = hipModuleLaunchKernel(e->fn[3], (unsigned)a.nblocks, 1, 1, ENC_BLOCK, 1, 1,
+                                   (unsigned)enc_write_lds_bytes(), stream, nullptr, extra);
+    } else if (write && e->fn[2]) { // the write pass on wave pairs (encode_write_pair_body)
         const int h = enc_pair_split(schema);
         rc = hipModuleLaunchKernel(e->fn[2], (unsigned)a.nblocks, 1, 1, ENC_PAIR_BLOCK, 1, 1,
                                    (unsigned)enc_pair_lds_bytes(h), stream, nullptr, extra);

@@ -1,5 +1,7 @@
 """The send path on the bench's 1M Flat16 records (272 MB framed): spec_frames_write against a
-device-to-device copy of the same bytes in the same run.  Writes profiles/<run>/egress.json.
+device-to-device copy of the same bytes in the same run (step "frames"), and the fused framed
+encoder spec_encode_flat_frames against spec_encode_flat alone and spec_encode_flat followed by
+spec_frames_write (step "fused").  Writes profiles/<run>/egress.json.
 
 Every GPU step is a child process of its own under a time limit; a step that fails or runs out
 of time ends the run (nothing more is started on the GPU).
@@ -16,7 +18,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-STEPS = (("frames", 240),)
+STEPS = (("frames", 240), ("fused", 300))
 SEED = 0x5EC0DE
 
 
@@ -60,6 +62,64 @@ def step_frames(n):
             "write_gb_s": round((stream.numel() + total + 16 * n) / (w_ms * 1e-3) / 1e9, 1),
             "d2d_copy_gb_s": round(2 * total / (c_ms * 1e-3) / 1e9, 1),
             "write_over_copy": round(w_ms / c_ms, 3), "ends_traffic_bytes": 16 * n, "ok": ok}
+
+
+def step_fused(n, rounds=5, reps=20):
+    """(a) spec_encode_flat, (b) spec_encode_flat + spec_frames_write, (c) spec_encode_flat_frames on
+    the same columns, timed in alternating rounds in one process.  Per leg: the mean of the rounds'
+    back-to-back means, the median of their medians, and [lowest p10, highest p90] over the rounds
+    (the widest spread seen, so "c's p90 below b's p10" holds for every pair of rounds)."""
+    import statistics
+
+    import torch
+
+    import bench
+    import spec_amd
+
+    dev = torch.device("cuda", 0)
+    _, _, d_cols, d_heaps, stream, ends = bench.make_batch(n, SEED, dev)
+    total = stream.numel() + 4 * n
+    enc = spec_amd.Encoder(spec_amd.FLAT16, n, dev)
+    s2, e2 = torch.empty_like(stream), torch.empty_like(ends)
+    out_b, fe_b = torch.empty(total, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+    out_c, fe_c = torch.empty(total, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+    L = spec_amd.lib()
+
+    def encode():
+        enc.encode_into(d_cols, d_heaps, s2, e2)
+
+    def two_pass():
+        enc.encode_into(d_cols, d_heaps, s2, e2)
+        rc = L.spec_frames_write(_p(s2), s2.numel(), _p(e2), n, _p(out_b), total, _p(fe_b),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, rc
+
+    def fused():
+        enc.encode_frames_into(d_cols, d_heaps, out_c, fe_c)
+
+    legs = {"encode": encode, "encode_then_frames_write": two_pass, "encode_frames": fused}
+    bench.gpu_prewarm(two_pass)
+    seen = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, fn in legs.items():
+            seen[k].append(bench.kernel_time_events(fn, reps, lead=3, spread=True))
+    two_pass()
+    fused()
+    torch.cuda.synchronize()
+    ok = bool(torch.equal(out_c, out_b)) and bool(torch.equal(fe_c, fe_b)) and int(enc.total.item()) == total
+    res = {"records": n, "stream_bytes": int(stream.numel()), "framed_bytes": int(total), "rounds": rounds,
+           "reps_per_round": reps}
+    for k, rs in seen.items():
+        res[k] = {"mean_ms": round(statistics.mean(r[0] for r in rs), 4),
+                  "median_ms": round(statistics.median(r[1] for r in rs), 4),
+                  "p10_p90_ms": [round(min(r[2] for r in rs), 4), round(max(r[3] for r in rs), 4)],
+                  "round_means_ms": [round(r[0], 4) for r in rs]}
+    a, b, c = res["encode"], res["encode_then_frames_write"], res["encode_frames"]
+    res["fused_over_encode"] = round(c["mean_ms"] / a["mean_ms"], 3)
+    res["fused_over_two_pass"] = round(c["mean_ms"] / b["mean_ms"], 3)
+    res["fused_p90_below_two_pass_p10"] = c["p10_p90_ms"][1] < b["p10_p90_ms"][0]
+    res["ok"] = ok
+    return res
 
 
 def main():
