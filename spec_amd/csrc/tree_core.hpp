@@ -627,8 +627,10 @@ struct DEmit {
     uint64_t pos;
     uint64_t lo;    // first byte of the row (bytes below belong to another row)
     uint32_t w = 0; // pending bytes of the dword holding pos
+    // (LSink: the dword holding the output's first bytes starts below byte 0 when the output is not
+    // 4-byte aligned: base is then "negative" (wrapped), so it is compared with lo as signed)
     __device__ __forceinline__ void store_word(uint64_t base, uint64_t end, uint32_t v) { // bytes [base, end) of v
-        k.word(base, base > lo ? base : lo, end, v);
+        k.word(base, (long long)base > (long long)lo ? base : lo, end, v);
     }
     __device__ __forceinline__ void store_pending(uint64_t base, uint64_t end) { store_word(base, end, w); }
     __device__ __forceinline__ void put1(uint32_t b) {
@@ -746,15 +748,19 @@ struct BEmit16 {
 
     // the position of pos within its 16-byte memory chunk
     __device__ __forceinline__ uint32_t phase(uint64_t p) const { return (uint32_t)(((unsigned long long)out + p) & 15); }
-    // bytes [max(base, lo), end) of the chunk at base (16-byte aligned in memory), end <= base + 16
+    // bytes [max(base, lo), end) of the chunk at base (16-byte aligned in memory), end <= base + 16.
+    // The chunk holding the output's first bytes starts below byte 0 when `out` is not 16-byte
+    // aligned: base is then "negative" (wrapped), so it is compared with lo as signed — an unsigned
+    // compare took it for a chunk inside the row and stored up to 15 bytes below out[0].
     __device__ __forceinline__ void store_chunk(uint64_t base, uint64_t end) {
-        if (base >= lo && end == base + 16) {
+        const bool inside = (long long)base >= (long long)lo;
+        if (inside && end == base + 16) {
             typedef unsigned int v4u __attribute__((ext_vector_type(4)));
             v4u v = {(uint32_t)c0, (uint32_t)(c0 >> 32), (uint32_t)c1, (uint32_t)(c1 >> 32)};
             *(v4u *)(out + base) = v;
             return;
         }
-        for (uint64_t q = base > lo ? base : lo; q < end;) {
+        for (uint64_t q = inside ? base : lo; q < end;) {
             const uint32_t k = (uint32_t)(q - base);
             const uint64_t word = k < 8 ? c0 : c1;
             const uint32_t sh = 8 * (k & 7);
