@@ -284,6 +284,20 @@ size_t spec_encode_tree_workspace_size(const spec_tree *tree, const uint64_t *ro
 int spec_encode_tree(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
                      const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap, uint64_t *ends,
                      void *workspace, size_t workspace_size, uint64_t *total, void *stream);
+/* spec_encode_tree_frames: spec_encode_tree with every record behind its mpx frame head
+ * (mpx/conn_writer.go:84-97), as spec_encode_flat_frames: record k becomes
+ * [u32 big-endian size_k][message_k], the frames back to back from frames[0] — exactly the bytes
+ * of spec_frames_write over spec_encode_tree's stream, from the encoder's own launches (the root
+ * table's writer emits the head with the record; child rows keep their absolute positions).
+ * frame_ends[k] = spec_encode_tree's ends[k] + 4(k + 1) (may be NULL).  *total (device) = the
+ * framed size = the unframed total + 4 rows[0], or all-ones on an encoder error; if it exceeds
+ * frames_cap nothing is written to frames/frame_ends; with frames == NULL only *total is
+ * computed.  Workspace, argument checks and return codes are spec_encode_tree's.  Any byte
+ * alignment of `frames`; nothing outside frames[0, *total) or frame_ends[0, rows[0]) is written. */
+int spec_encode_tree_frames(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
+                            const uint64_t *heap_lens, const uint64_t *rows, uint8_t *frames, uint64_t frames_cap,
+                            uint64_t *frame_ends, void *workspace, size_t workspace_size, uint64_t *total,
+                            void *stream);
 
 /* ---- several devices in one process (the reference has no multi-device code) ----
  * Records are independent, so a batch splits into contiguous record shards, one per device.  A
@@ -720,6 +734,23 @@ int spec_encode_nested(const spec_nested_schema *schema, const void *const *oute
                        const void *const *item_columns, const uint8_t *const *item_heaps,
                        const uint64_t *item_heap_lens, uint64_t nitems, uint64_t n, uint8_t *out, uint64_t out_cap,
                        uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total, void *stream);
+/* spec_encode_nested_frames: spec_encode_nested with every record behind its mpx frame head
+ * (mpx/conn_writer.go:84-97), as spec_encode_flat_frames: record k becomes
+ * [u32 big-endian size_k][message_k], the frames back to back from frames[0] — exactly the bytes
+ * of spec_frames_write over spec_encode_nested's stream, from the encoder's own three launches
+ * (with either workspace size).  frame_ends[k] = spec_encode_nested's ends[k] + 4(k + 1).
+ * *total (device) = the framed size = the unframed total + 4n, or all-ones on an encoder error;
+ * if it exceeds frames_cap nothing is written to frames/frame_ends; with frames == NULL only
+ * *total is computed; n == 0 writes *total = 0 and nothing else.  Workspace sizes, argument
+ * checks and return codes are spec_encode_nested's.  Asynchronous, no host synchronisation.  Any
+ * byte alignment of `frames`; nothing outside frames[0, *total) or frame_ends[0, n) is written.
+ * Positions are 64-bit. */
+int spec_encode_nested_frames(const spec_nested_schema *schema, const void *const *outer_columns,
+                              const uint8_t *const *outer_heaps, const uint64_t *outer_heap_lens,
+                              const uint32_t *item_begin, const void *const *item_columns,
+                              const uint8_t *const *item_heaps, const uint64_t *item_heap_lens, uint64_t nitems,
+                              uint64_t n, uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends, void *workspace,
+                              size_t workspace_size, uint64_t *total, void *stream);
 /* spec_encode_nested_jit_compile: diagnostic — the hiprtc compile (no GPU needed) of the
  * schema-specialised nested encode kernels; code-object size, 0 if neither schema has one. */
 long long spec_encode_nested_jit_compile(const spec_nested_schema *schema);

@@ -11,16 +11,17 @@ from .batch import (PARSE_LIST, PARSE_MESSAGE, PARSE_VALUE, Columns, Decoder, En
 from . import lz4
 from .frames import decode_frames, frames_index, frames_index_device, make_frames, make_frames_device, write_frames
 from .pipeline import HostDecoder
-from .nested import NestedColumns, NestedDecoder, NestedEncoder, decode_nested, encode_nested
+from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, encode_nested,
+                     encode_nested_frames)
 from .schema import FLAT16, NESTED, Field, Kind, NestedSchema, Schema
 from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, TreeEncoder, decode_tree, decode_values,
-                   encode_tree, pkg1_message, pkg1_tree, tree_rows)
+                   encode_tree, encode_tree_frames, pkg1_message, pkg1_tree, tree_rows)
 
 __all__ = [
     "HostDecoder", "decode_frames", "frames_index", "frames_index_device", "make_frames", "make_frames_device", "write_frames", "LIB_PATH", "SpecError", "header_symbols", "lib", "set_jit", "Columns", "Decoder", "Encoder", "alloc_columns",
     "decode_flat", "decode_flat_errors", "encode_flat", "encode_flat_frames", "parse_messages", "PARSE_MESSAGE", "PARSE_LIST", "PARSE_VALUE",
     "FLAT16", "Field", "Kind", "Schema",
     "NESTED", "NestedSchema", "NestedColumns", "NestedDecoder", "NestedEncoder", "decode_nested",
-    "encode_nested", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
-    "decode_values", "encode_tree", "pkg1_message", "pkg1_tree", "tree_rows",
+    "encode_nested", "encode_nested_frames", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
+    "decode_values", "encode_tree", "encode_tree_frames", "pkg1_message", "pkg1_tree", "tree_rows",
 ]

@@ -163,6 +163,7 @@ def _declare(L):
     L.spec_encode_nested.argtypes = [C.POINTER(SpecNestedSchema), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64),
                                      vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64,
                                      vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp]
+    L.spec_encode_nested_frames.argtypes = L.spec_encode_nested.argtypes
     for name in ("spec_device_free", "spec_host_free", "spec_stream_destroy", "spec_stream_sync"):
         getattr(L, name).argtypes = [vp]
     L.spec_device_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
@@ -246,6 +247,7 @@ def _declare(L):
     L.spec_encode_tree_workspace_size.restype = C.c_size_t
     L.spec_encode_tree.argtypes = [C.POINTER(SpecTree), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp]
+    L.spec_encode_tree_frames.argtypes = L.spec_encode_tree.argtypes
 
 
 def strerror(rc: int) -> str:

@@ -735,7 +735,7 @@ static int nested_encode_wide(const spec_nested_schema *schema, uint32_t list_f,
                               const uint32_t *item_begin, const void *const *item_columns,
                               const uint8_t *const *item_heaps, const uint64_t *item_heap_lens, uint64_t nitems,
                               uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *ends, uint64_t *total,
-                              hipStream_t st) {
+                              hipStream_t st, uint32_t frame_head) {
     const uint32_t no = schema->outer.nfields, ni = schema->item.nfields;
     if (no + ni > SPEC_TREE_MAX_FIELDS) return SPEC_E_INVALID_ARGUMENT;
     std::vector<spec_tree> tv(1);
@@ -794,16 +794,20 @@ static int nested_encode_wide(const spec_nested_schema *schema, uint32_t list_f,
     int rc = SPEC_OK;
     if (hipMemsetAsync(present, 1, std::max<uint64_t>(n, 1), st) != hipSuccess) rc = hip_rc(hipGetLastError());
     if (!rc)
-        rc = spec_encode_tree(&T, tc.data(), th.data(), tl.data(), rows, out, out_cap, ends, scratch, tws, total, st);
+        rc = spec::encode_tree_passes(&T, tc.data(), th.data(), tl.data(), rows, out, out_cap, ends, scratch, tws, total,
+                                      st, frame_head);
     if (hipFreeAsync(scratch, st) != hipSuccess && !rc) rc = hip_rc(hipGetLastError());
     return rc;
 }
 
-int spec_encode_nested(const spec_nested_schema *schema, const void *const *outer_columns,
-                       const uint8_t *const *outer_heaps, const uint64_t *outer_heap_lens, const uint32_t *item_begin,
-                       const void *const *item_columns, const uint8_t *const *item_heaps,
-                       const uint64_t *item_heap_lens, uint64_t nitems, uint64_t n, uint8_t *out, uint64_t out_cap,
-                       uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total, void *stream) {
+// spec_encode_nested (frame_head 0) and spec_encode_nested_frames (4: every record behind its mpx
+// frame head, from the framed instantiations of the scan and the write pass)
+static int encode_nested_impl(const spec_nested_schema *schema, const void *const *outer_columns,
+                              const uint8_t *const *outer_heaps, const uint64_t *outer_heap_lens,
+                              const uint32_t *item_begin, const void *const *item_columns,
+                              const uint8_t *const *item_heaps, const uint64_t *item_heap_lens, uint64_t nitems,
+                              uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *ends, void *workspace,
+                              size_t workspace_size, uint64_t *total, void *stream, uint32_t frame_head) {
     uint32_t list_f = 0;
     int rc = check_nested(schema, &list_f);
     if (rc) return rc;
@@ -815,7 +819,8 @@ int spec_encode_nested(const spec_nested_schema *schema, const void *const *oute
         for (uint32_t f = 0; f < schema->outer.nfields && n; f++)
             if (f != list_f && !outer_columns[f]) return SPEC_E_INVALID_ARGUMENT;
         return nested_encode_wide(schema, list_f, outer_columns, outer_heaps, outer_heap_lens, item_begin, item_columns,
-                                  item_heaps, item_heap_lens, nitems, n, out, out_cap, ends, total, (hipStream_t)stream);
+                                  item_heaps, item_heap_lens, nitems, n, out, out_cap, ends, total, (hipStream_t)stream,
+                                  frame_head);
     }
     spec::NestedEncodeArgs a{};
     memset(&a, 0, sizeof(a));
@@ -830,6 +835,7 @@ int spec_encode_nested(const spec_nested_schema *schema, const void *const *oute
     a.item_begin = item_begin;
     a.nitems = nitems;
     a.check_heaps = 1;
+    a.frame_head = frame_head;
     a.out = out;
     a.out_cap = out ? out_cap : 0;
     a.ends = ends;
@@ -843,6 +849,28 @@ int spec_encode_nested(const spec_nested_schema *schema, const void *const *oute
     if (spec::launch_nested_encode(schema, a, out != nullptr, (hipStream_t)stream))
         return hip_rc(hipGetLastError());
     return SPEC_OK;
+}
+
+int spec_encode_nested(const spec_nested_schema *schema, const void *const *outer_columns,
+                       const uint8_t *const *outer_heaps, const uint64_t *outer_heap_lens, const uint32_t *item_begin,
+                       const void *const *item_columns, const uint8_t *const *item_heaps,
+                       const uint64_t *item_heap_lens, uint64_t nitems, uint64_t n, uint8_t *out, uint64_t out_cap,
+                       uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total, void *stream) {
+    return encode_nested_impl(schema, outer_columns, outer_heaps, outer_heap_lens, item_begin, item_columns, item_heaps,
+                              item_heap_lens, nitems, n, out, out_cap, ends, workspace, workspace_size, total, stream, 0);
+}
+
+// spec_encode_nested with every record behind its mpx frame head (mpx/conn_writer.go:84-97): the
+// bytes of spec_frames_write over spec_encode_nested's stream, from the encoder's three launches
+int spec_encode_nested_frames(const spec_nested_schema *schema, const void *const *outer_columns,
+                              const uint8_t *const *outer_heaps, const uint64_t *outer_heap_lens,
+                              const uint32_t *item_begin, const void *const *item_columns,
+                              const uint8_t *const *item_heaps, const uint64_t *item_heap_lens, uint64_t nitems,
+                              uint64_t n, uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends, void *workspace,
+                              size_t workspace_size, uint64_t *total, void *stream) {
+    return encode_nested_impl(schema, outer_columns, outer_heaps, outer_heap_lens, item_begin, item_columns, item_heaps,
+                              item_heap_lens, nitems, n, frames, frames_cap, frame_ends, workspace, workspace_size, total,
+                              stream, 4);
 }
 
 size_t spec_encode_flat_workspace_size(uint64_t n) { return enc_ws_sums(n) + WIDE_FIELDS_BYTES; }

@@ -3,6 +3,8 @@
 // launcher, which prefers the schema-specialised kernels of jit.cpp.  Device code and the
 // algorithm: encode_nested_core.hpp.  Three launches, no host sync: sizes -> scan of block
 // sums -> write.
+// spec_encode_nested_frames (NestedEncodeArgs::frame_head = 4) runs the same three launches with
+// the framed instantiations of the scan and the write pass: the unframed kernels do not change.
 #include <hip/hip_runtime.h>
 
 #include "encode_nested_core.hpp"
@@ -26,6 +28,16 @@ __global__ __launch_bounds__(NENC_BLOCK) void nested_enc_write_kernel(NestedEnco
     nested_enc_write_body<RuntimeEnc, RuntimeEnc>(a, smem);
 }
 
+// the framed encoder: 4 more bytes per record in every block sum, the head in front of every record
+__global__ __launch_bounds__(1024) void nested_enc_scan_frames_kernel(NestedEncodeArgs a) {
+    scan_block_sums<4>(a.block_sums, a.nblocks, a.total, a.n);
+}
+
+__global__ __launch_bounds__(NENC_BLOCK) void nested_enc_write_frames_kernel(NestedEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    nested_enc_write_body<RuntimeEnc, RuntimeEnc, 4>(a, smem);
+}
+
 } // namespace
 
 int launch_nested_encode(const spec_nested_schema *schema, const NestedEncodeArgs &a, bool write,
@@ -37,11 +49,15 @@ int launch_nested_encode(const spec_nested_schema *schema, const NestedEncodeArg
             hipLaunchKernelGGL(nested_enc_size_kernel, dim3((unsigned)a.nblocks), dim3(NENC_BLOCK),
                                nenc_size_lds_bytes(), stream, a);
     }
-    hipLaunchKernelGGL(nested_enc_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+    if (a.frame_head) hipLaunchKernelGGL(nested_enc_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a);
+    else hipLaunchKernelGGL(nested_enc_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
     if (write && a.nblocks) {
         const int j = jit_launch_nested_encode(schema, a, true, stream);
         if (j < 0) return -1;
-        if (j == 0)
+        if (j == 0 && a.frame_head)
+            hipLaunchKernelGGL(nested_enc_write_frames_kernel, dim3((unsigned)a.nblocks), dim3(NENC_BLOCK),
+                               nenc_write_lds_bytes(), stream, a);
+        else if (j == 0)
             hipLaunchKernelGGL(nested_enc_write_kernel, dim3((unsigned)a.nblocks), dim3(NENC_BLOCK),
                                nenc_write_lds_bytes(), stream, a);
     }

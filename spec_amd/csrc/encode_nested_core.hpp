@@ -48,6 +48,7 @@ struct NestedEncodeArgs {
     uint64_t nblocks;
     uint64_t *total;
     uint32_t xcd; // write pass: 1 = XCD-aware block order (grid padded to a multiple of 8)
+    uint32_t frame_head; // 0, or 4: every record behind its mpx frame head (selects the framed kernels)
     // optional (workspace large enough): the size pass leaves every item's wave prefix
     // (item_pre[i] = bytes of the wave's items up to and including item i) and each wave's
     // item-parallel verdict (wave_ok), so the write pass reads them instead of reloading every
@@ -65,6 +66,19 @@ constexpr int NENC_WAVE_LDS = NENC_PRE + NENC_SLAB;
 constexpr size_t nenc_size_lds_bytes() { return NENC_HEAD + (size_t)(NENC_BLOCK / 64) * NENC_PRE; }
 constexpr size_t nenc_write_lds_bytes() { return NENC_HEAD + (size_t)(NENC_BLOCK / 64) * NENC_WAVE_LDS; }
 static_assert(NENC_PRE % 16 == 0 && NENC_WAVE_LDS % 16 == 0, "slab alignment");
+static_assert(NENC_BLOCK == ENC_BLOCK, "scan_block_sums<HEAD> counts ENC_BLOCK records per block");
+
+// HEAD = 4: the mpx frame head (u32 BE message size, mpx/conn_writer.go:84-97) at p, by an
+// emitter that touches nothing outside [p, p + 4)
+template <int HEAD, class Sink, class Pos>
+__device__ __forceinline__ void emit_frame_head(const Sink &k, Pos p, uint64_t size) {
+    if constexpr (HEAD != 0) {
+        static_assert(HEAD == 4, "the frame head is a u32");
+        Emit<Sink, Pos> hd(k, p);
+        hd.put4(bswap32((uint32_t)size));
+        hd.finish();
+    }
+}
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -343,7 +357,13 @@ __device__ __forceinline__ void nested_enc_size_body(const NestedEncodeArgs &a, 
 }
 
 // Pass 3: record offsets from the block scan, ends[], the records' bytes.
-template <class OP, class IP>
+// HEAD = 4 (spec_encode_nested_frames): every record is [u32 BE size][message]; the scanned size
+// of a record is its message's + HEAD, the block offsets and the total come from
+// scan_block_sums<HEAD>, ends[] are frame ends and [S, E) is the framed span of the wave (the slab
+// fit counts the heads).  The head is the first append of the record's emitter (OP::emit<HEAD>),
+// so the list start and the items' slab positions move with the record.  HEAD = 0 is the
+// unframed encoder, instruction for instruction.
+template <class OP, class IP, int HEAD = 0>
 __device__ __forceinline__ void nested_enc_write_body(const NestedEncodeArgs &a, uint8_t *smem) {
     uint64_t *wsum = (uint64_t *)smem;
     uint8_t *inv_outer = smem + 32, *inv_item = smem + 96;
@@ -370,7 +390,8 @@ __device__ __forceinline__ void nested_enc_write_body(const NestedEncodeArgs &a,
     ListSize ls;
     RecSize rs = lane_record_size<OP>(a, L, orec, pre, false, err, ls);
     if (!L.valid) rs.total = 0;
-    uint64_t x = rs.total; // block exclusive scan of sizes
+    const uint64_t sz = rs.total + (L.valid ? HEAD : 0); // the record's bytes in the output
+    uint64_t x = sz; // block exclusive scan of sizes
     for (int o = 1; o < 64; o <<= 1) {
         const uint64_t y = __shfl_up(x, o);
         if (lane >= o) x += y;
@@ -379,15 +400,15 @@ __device__ __forceinline__ void nested_enc_write_body(const NestedEncodeArgs &a,
     lds_barrier();
     uint64_t pre_b = blk_pre;
     for (int w = 0; w < wave; w++) pre_b += wsum[w];
-    const uint64_t start = pre_b + x - rs.total;
-    if (L.valid) a.ends[L.r] = start + rs.total;
+    const uint64_t start = pre_b + x - sz;
+    if (L.valid) a.ends[L.r] = start + sz;
 
     const uint64_t wbase = blk * NENC_BLOCK + wave * 64;
     if (wbase >= a.n) return;
     const uint64_t S = __builtin_amdgcn_readfirstlane((uint32_t)start) |
                        ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(start >> 32)) << 32);
     const int last = (int)((a.n - wbase) < 64 ? a.n - wbase - 1 : 63);
-    const uint64_t Ev = __shfl(start + rs.total, last);
+    const uint64_t Ev = __shfl(start + sz, last);
     const uint64_t E = __builtin_amdgcn_readfirstlane((uint32_t)Ev) |
                        ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(Ev >> 32)) << 32);
     const uint64_t head = ((uint64_t)(a.out + S)) & 15; // slab pos of byte S keeps 16-B phase
@@ -395,14 +416,15 @@ __device__ __forceinline__ void nested_enc_write_body(const NestedEncodeArgs &a,
         if (L.valid) {
             GlobalSink k{a.out};
             ListEmitter<GlobalSink, long long> le{&a, &k, inv_item};
-            emit_message(a.outer, k, (long long)start, L.r, rs, inv_outer, le);
+            emit_frame_head<HEAD>(k, (long long)start, rs.total);
+            emit_message(a.outer, k, (long long)start + HEAD, L.r, rs, inv_outer, le);
         }
         return;
     }
     LdsSink k{slab, (int)(smem + 160 - slab)}; // dummy dword in the header
     // A: outer records, the items skipped
     WaveListEmit le{pre + (L.b - L.I0), ls.count, (uint32_t)ls.data, ls.big, 0};
-    if (L.valid) OP::emit(a.outer, k, (int)(head + (start - S)), L.r, orec, rs, inv_outer, le);
+    if (L.valid) OP::template emit<HEAD>(a.outer, k, (int)(head + (start - S)), L.r, orec, rs, inv_outer, le);
     wave_sync();
     const int lst = le.lstart;
     const bool fix = L.valid && ls.count > 0 && (lst & 3);
@@ -496,6 +518,9 @@ __device__ __forceinline__ void emit_item_range(const NestedEncodeArgs &a, const
 // later in chunk order, as in the one-wave pass), the record's A1 tail (kept pending across the
 // barrier, then stored bytewise) or the previous record's A2 bytes (emitted after the barrier).
 // The split is at a record boundary, so no item byte is covered by the other wave's stores.
+// HEAD = 4 (spec_encode_nested_frames, as nested_enc_write_body): the frame head is A1's first
+// append, in front of the fields before the list — with the list as the first field it is all of
+// A1, and the <= 3 of its bytes an item's first dword store may cover are A1's pending tail.
 #ifndef SPEC_AB_NENC_SPLIT
 #define SPEC_AB_NENC_SPLIT 45
 #endif
@@ -503,7 +528,7 @@ __device__ __forceinline__ void emit_item_range(const NestedEncodeArgs &a, const
 #ifndef SPEC_AB_NENC_SKIP
 #define SPEC_AB_NENC_SKIP 0
 #endif
-template <class OP, class IP>
+template <class OP, class IP, int HEAD = 0>
 __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArgs &a, uint8_t *smem) {
     constexpr int LF = OP::list_field();
     static_assert(LF >= 0, "the outer schema holds the list field");
@@ -549,7 +574,8 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
         rs = lane_record_size<OP>(a, L, orec, pre, false, err, ls);
         if (!valid) rs.total = 0;
     }
-    uint64_t x = rs.total; // group exclusive scan of sizes (wave 0)
+    const uint64_t sz = rs.total + (half == 0 && valid ? HEAD : 0); // the record's bytes in the output
+    uint64_t x = sz; // group exclusive scan of sizes (wave 0)
     for (int o = 1; o < 64; o <<= 1) {
         const uint64_t y = __shfl_up(x, o);
         if (lane >= o) x += y;
@@ -559,17 +585,17 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
     uint64_t S = blk_pre;
     for (int g = 0; g < grp; g++) S += wsum[g];
     const uint64_t E = S + wsum[grp];
-    const uint64_t start = S + x - rs.total; // (wave 0)
+    const uint64_t start = S + x - sz; // (wave 0)
     const uint64_t head = ((uint64_t)(a.out + S)) & 15;
     const bool staged = live && fast && head + (E - S) + 16 <= (uint64_t)NENC_SLAB; // group-uniform
-    if (half == 0 && valid) a.ends[r] = start + rs.total;
-    const int p0 = (int)(head + (start - S));
+    if (half == 0 && valid) a.ends[r] = start + sz;
+    const int p0 = (int)(head + (start - S)), m0 = p0 + HEAD; // the record's first byte, its message's
     int lst = 0;
     if (half == 0 && staged && valid) {
         // the list's slab position from the sizes of the fields before it; the record's prefix
         // entries become its items' slab positions
         bool e1 = false;
-        lst = p0 + (int)OP::template data_size<0, KnownListSize, LF>(a.outer, orec, r, false, e1, KnownListSize{0});
+        lst = m0 + (int)OP::template data_size<0, KnownListSize, LF>(a.outer, orec, r, false, e1, KnownListSize{0});
         if (ls.count > 0) {
             const uint32_t k0 = b - I0, k1 = e - I0;
             const int delta = lst - (int)pre[k0];
@@ -588,7 +614,10 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
     Emit<LdsSink, int, true> em(k, p0);
     if (staged) {
         if (half == 0) {
-            if (valid && !(SPEC_AB_NENC_SKIP & 4)) OP::template emit_range<0, LF>(a.outer, em, xo, p0, r); // A1, its tail left pending
+            if (valid && !(SPEC_AB_NENC_SKIP & 4)) { // A1, its tail left pending
+                if constexpr (HEAD != 0) em.put4(bswap32((uint32_t)rs.total));
+                OP::template emit_range<0, LF>(a.outer, em, xo, m0, r);
+            }
             if (!(SPEC_AB_NENC_SKIP & 1)) emit_item_range<IP>(a, k, pre, I0, 0u, K0, inv_item, lane);
         } else if (!(SPEC_AB_NENC_SKIP & 1)) {
             emit_item_range<IP>(a, k, pre, I0, K0, cnt, inv_item, lane);
@@ -598,14 +627,15 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
         // straight to HBM on its lane
         GlobalSink g{a.out};
         ListEmitter<GlobalSink, long long> le{&a, &g, inv_item};
-        emit_message(a.outer, g, (long long)start, r, rs, inv_outer, le);
+        emit_frame_head<HEAD>(g, (long long)start, rs.total);
+        emit_message(a.outer, g, (long long)start + HEAD, r, rs, inv_outer, le);
     }
     __syncthreads(); // (4) every whole-dword store of A1 and of the items is done
     if (staged && half == 0 && valid && !(SPEC_AB_NENC_SKIP & 4)) {
         // A2: the same emitter from the list field on; the hook stores A1's pending tail bytewise
         // and resumes past the items with their last bytes read back (WaveListEmit merge_slab)
         WaveListEmit le{pre + (b - I0), ls.count, (uint32_t)ls.data, ls.big, 0, slab};
-        OP::template emit_range<LF, OP::N>(a.outer, em, xo, p0, r, le);
+        OP::template emit_range<LF, OP::N>(a.outer, em, xo, m0, r, le);
         OP::emit_table_trailer(em, xo, rs);
         em.finish();
     }

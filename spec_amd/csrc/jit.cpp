@@ -268,10 +268,18 @@ std::string generate_nested_encode(const spec_nested_schema *s) {
       << "extern \"C\" __global__ __launch_bounds__(256) void spec_encode_nested_write_jit(spec::NestedEncodeArgs a) {\n"
       << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
       << "  spec::nested_enc_write_body<OP, IP>(a, smem);\n}\n";
+    // spec_encode_nested_frames: the same write passes with the 4-byte mpx frame head per record,
+    // further instantiations in the same module (the unframed kernels' code does not change)
+    o << "extern \"C\" __global__ __launch_bounds__(256) void spec_encode_nested_write_frames_jit(spec::NestedEncodeArgs a) {\n"
+      << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
+      << "  spec::nested_enc_write_body<OP, IP, 4>(a, smem);\n}\n";
     if (fo) // the write pass on wave pairs (needs the outer list field at a constant index)
         o << "extern \"C\" __global__ __launch_bounds__(512) void spec_encode_nested_write_pair_jit(spec::NestedEncodeArgs a) {\n"
           << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
-          << "  spec::nested_enc_write_pair_body<OP, IP>(a, smem);\n}\n";
+          << "  spec::nested_enc_write_pair_body<OP, IP>(a, smem);\n}\n"
+          << "extern \"C\" __global__ __launch_bounds__(512) void spec_encode_nested_write_pair_frames_jit(spec::NestedEncodeArgs a) {\n"
+          << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
+          << "  spec::nested_enc_write_pair_body<OP, IP, 4>(a, smem);\n}\n";
     return o.str();
 }
 
@@ -495,7 +503,8 @@ Entry load(const std::vector<char> &code, Prog p) {
                                 "spec_encode_write_frames_jit"},
                                {"spec_decode_nested_jit", "spec_decode_nested2_jit", "spec_decode_nested3_jit",
                                 "spec_decode_nested_pair_jit"},
-                               {"spec_encode_nested_size_jit", "spec_encode_nested_write_jit", nullptr, nullptr}};
+                               {"spec_encode_nested_size_jit", "spec_encode_nested_write_jit", nullptr, // ([2], [4]: the pair kernels)
+                                "spec_encode_nested_write_frames_jit"}};
     bool ok = hipModuleLoadData(&e.mod, code.data()) == hipSuccess;
     if (ok && p == DECODE && hipModuleGetFunction(&e.fn[0], e.mod, names[p][0]) != hipSuccess) {
         (void)hipGetLastError(); // a wide / big-table schema (generate_decode): its own kernel names
@@ -518,6 +527,11 @@ Entry load(const std::vector<char> &code, Prog p) {
         hipModuleGetFunction(&e.fn[2], e.mod, "spec_encode_nested_write_pair_jit") != hipSuccess) {
         (void)hipGetLastError(); // no specialised outer encoder: no pair kernel
         e.fn[2] = nullptr;
+    }
+    if (ok && p == NESTED_ENC && e.fn[2] &&
+        hipModuleGetFunction(&e.fn[4], e.mod, "spec_encode_nested_write_pair_frames_jit") != hipSuccess) {
+        (void)hipGetLastError();
+        ok = false; // the pair kernels are generated together
     }
     if (!ok) {
         (void)hipGetLastError();
@@ -1453,7 +1467,11 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
         for (uint32_t k = cut[b]; k < cut[b + 1]; k++) gen_field_loads(o, D, T, k, true, "  ");
         if (b == 0) o << "  if (B.ends_out) B.ends_out[row] = start + B.size[0][row];\n";
         o << "  const bool big = (m & 0x" << std::hex << bigm << std::dec << "ull) != 0 || (m != 0 && data > 65535);\n"
-          << "  auto em = mk(start + off);\n  uint32_t nf = 0;\n  bool bigtag = false;\n";
+          // (block 0 of a framed record starts with its head, B.frame_head bytes below the message)
+          << (b ? "  auto em = mk(start + off);\n"
+                : "  const uint32_t fh = B.frame_head;\n  auto em = mk(start - fh);\n"
+                  "  if (fh) em.be(B.size[0][row], 4);\n")
+          << "  uint32_t nf = 0;\n  bool bigtag = false;\n";
         for (uint32_t k = cut[b]; k < cut[b + 1]; k++) gen_field_write(o, D, T, k, true);
         o << "  em.finish();\n  const uint64_t tb = start + data;\n";
         for (uint32_t k = cut[b]; k < cut[b + 1]; k++) {
@@ -1582,7 +1600,8 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
       << "  const uint64_t r1 = r0 + 64 < n ? r0 + 64 : n;\n"
       << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
       << "  TileU8 *img = (TileU8 *)smem;\n"
-      << "  const uint64_t org = B.offsets[r0], fin = B.offsets[r1 - 1] + B.size[0][r1 - 1];\n"
+      // (the image starts at the first record's frame head, B.frame_head bytes below its message)
+      << "  const uint64_t org = B.offsets[r0] - B.frame_head, fin = B.offsets[r1 - 1] + B.size[0][r1 - 1];\n"
       // (out + sh 16-byte aligned: the image's chunks are the output's)
       << "  const uint64_t sh = org - (((unsigned long long)B.out + org) & 15);\n"
       << (SPEC_AB_TILE_OR ? "  tile_clear(img, fin - sh < cap ? (uint32_t)(fin - sh) : cap);\n  __syncthreads();\n" : "")
@@ -1665,7 +1684,12 @@ std::string generate_tree(const TreeDesc &D, bool *has) {
                   // the records' rows are long: 16-byte chunk stores (BEmit16); the shorter rows of
                   // the tables below them keep the dword emitter (measured on pkg1: records 170 ->
                   // 134 us with BEmit16, the depth-1 tables 159 -> 180 us)
-                  << (t == 0 ? "      BEmit16 em{B.out, start, start};\n" : "      BEmit em{{B.out}, start, start};\n")
+                  // (a framed record: its head is the first append of its emitter, which owns
+                  // [start - 4, end))
+                  << (t == 0 ? "      const uint32_t fh = B.frame_head;\n"
+                               "      BEmit16 em{B.out, start - fh, start - fh};\n"
+                               "      if (fh) em.be(B.size[0][row], 4);\n"
+                             : "      BEmit em{{B.out}, start, start};\n")
                   << "      gen_wrow_" << t << "(em, D, B, row, start);\n"
                   << "    }\n    break;\n";
         o << "  default:\n"
@@ -1972,8 +1996,10 @@ int jit_launch_nested_encode(const spec_nested_schema *schema, const NestedEncod
     const unsigned grid = (unsigned)(args.xcd ? (a.nblocks + 7) / 8 * 8 : a.nblocks);
     // the write pass on wave pairs when the size pass left its item prefixes (nested_enc_write_pair_body)
     const bool pair = write && SPEC_AB_NENC_PAIR && e->fn[2] && a.item_pre && a.wave_ok;
-    hipError_t rc = hipModuleLaunchKernel(e->fn[pair ? 2 : write ? 1 : 0], grid, 1, 1, pair ? 2 * NENC_BLOCK : NENC_BLOCK,
-                                          1, 1, lds, stream, nullptr, extra);
+    // (the framed write pass, a.frame_head: the framed instantiation of the same kernel)
+    const int which = !write ? 0 : a.frame_head ? (pair ? 4 : 3) : (pair ? 2 : 1);
+    hipError_t rc = hipModuleLaunchKernel(e->fn[which], grid, 1, 1, pair ? 2 * NENC_BLOCK : NENC_BLOCK, 1, 1, lds, stream,
+                                          nullptr, extra);
     return rc == hipSuccess ? 1 : -1;
 }
 

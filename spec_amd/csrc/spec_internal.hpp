@@ -125,5 +125,9 @@ int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write
 struct TreeDesc;
 const hipFunction_t *jit_tree_kernels(const TreeDesc &D);
 long long jit_compile_only_tree(const TreeDesc &D);
+// tree.hip: spec_encode_tree (frame_head 0) / spec_encode_tree_frames (4)
+int encode_tree_passes(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
+                       const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap, uint64_t *ends,
+                       void *workspace, size_t workspace_size, uint64_t *total, void *stream, uint32_t frame_head);
 
 } // namespace spec

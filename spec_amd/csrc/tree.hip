@@ -91,7 +91,11 @@ __global__ __launch_bounds__(TB) void tree_write_kernel(const TreeDesc *Dp, cons
         const uint64_t start = x == 0 ? B.offsets[row] : B.pos[x][row];
         if (start == ~0ull) continue; // a row no written owner placed (absent message / list)
         if (x == 0 && B.ends_out) B.ends_out[row] = start + B.size[0][row];
-        BEmit em{{B.out}, start, start};
+        // a framed record's head (mpx/conn_writer.go:84-97) is the first append of its own emitter,
+        // which then owns [start - 4, end): nothing below the head is touched
+        const uint32_t fh = x == 0 ? B.frame_head : 0u;
+        BEmit em{{B.out}, start - fh, start - fh};
+        if (fh) em.be(B.size[0][row], 4);
         if (T.shape == SHAPE_VALUE) {
             const TField &F = D.f[T.field];
             emit_value(em, B, D, F.col, F.elem, row);
@@ -195,13 +199,15 @@ __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *sh, ui
     return r;
 }
 
-// pass 1: tile sums of a u32 array
-__global__ __launch_bounds__(SCAN_T) void scan_tiles_kernel(const uint32_t *in, uint64_t n, uint64_t *tile_sums) {
+// pass 1: tile sums of a u32 array; every element counts `add` more (the framed encoder's head
+// per record, 0 otherwise)
+__global__ __launch_bounds__(SCAN_T) void scan_tiles_kernel(const uint32_t *in, uint64_t n, uint64_t *tile_sums,
+                                                            uint32_t add) {
     __shared__ uint64_t sh[17];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER;
     uint64_t v = 0;
     for (int k = 0; k < SCAN_PER; k++)
-        if (base + k < n) v += in[base + k];
+        if (base + k < n) v += (uint64_t)in[base + k] + add;
     uint64_t tot;
     block_excl_scan(v, sh, tot);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = tot;
@@ -224,20 +230,23 @@ __global__ __launch_bounds__(SCAN_T) void scan_top_kernel(uint64_t *tile_sums, u
 }
 
 // pass 3: per tile, the exclusive prefix of every element: into out32 (u32, + out32[n] = total)
-// or out64 (u64); ends64 (optional) = prefix + element.  fold (up to FOLD_TILES tiles, no pass 2):
+// or out64 (u64); ends64 (optional) = prefix + element.  add: every element is `add` bytes
+// longer than in[] says, the extra bytes in FRONT of it — the prefixes written are the elements'
+// own starts, past their heads (the framed tree encoder: message starts).  fold (up to FOLD_TILES tiles, no pass 2):
 // the tile's offset is the sum of the earlier tiles' totals, summed by the block itself (one load
 // per thread), and block 0 sums every tile into *total (all-ones when *err).
 constexpr uint64_t FOLD_TILES = 1024;
 __global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const uint32_t *in, uint64_t n, const uint64_t *tile_sums,
                                                             uint64_t *total, uint32_t *out32, uint64_t *out64,
-                                                            uint64_t *ends64, uint32_t fold, const uint32_t *err) {
+                                                            uint64_t *ends64, uint32_t fold, const uint32_t *err,
+                                                            uint32_t add) {
     __shared__ uint64_t sh[17];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_PER;
     uint32_t v[SCAN_PER];
     uint64_t sum = 0;
     for (int k = 0; k < SCAN_PER; k++) {
         v[k] = base + k < n ? in[base + k] : 0;
-        sum += v[k];
+        sum += base + k < n ? (uint64_t)v[k] + add : 0;
     }
     uint64_t tot, off = 0, grand = 0;
     if (fold) {
@@ -253,6 +262,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const uint32_t *in, 
     }
     uint64_t p = off + block_excl_scan(sum, sh, tot);
     for (int k = 0; k < SCAN_PER; k++) {
+        p += add;
         if (base + k < n) {
             if (out32) out32[base + k] = (uint32_t)p;
             if (out64) out64[base + k] = p;
@@ -277,15 +287,15 @@ __global__ __launch_bounds__(256) void tree_pos_fill_kernel(PosFill f) {
 size_t scan_ws_bytes(uint64_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 1) * sizeof(uint64_t); }
 
 // exclusive scan of in[0, n) (in place allowed for out32); *total (device) = the sum, or all-ones
-// when *err (optional) is set
+// when *err (optional) is set.  add: `add` bytes in front of every element (scan_apply_kernel)
 int launch_scan(const uint32_t *in, uint64_t n, uint32_t *out32, uint64_t *out64, uint64_t *ends64, uint64_t *ws,
-                uint64_t *total, const uint32_t *err, hipStream_t st) {
+                uint64_t *total, const uint32_t *err, hipStream_t st, uint32_t add = 0) {
     const uint64_t tiles = std::max<uint64_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
     const uint32_t fold = tiles <= FOLD_TILES ? 1u : 0u;
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, in, n, ws);
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, in, n, ws, add);
     if (!fold) hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_T), 0, st, ws, tiles, total, err);
     hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, in, n, ws, total, out32, out64,
-                       ends64, fold, err);
+                       ends64, fold, err, add);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -576,9 +586,14 @@ size_t spec_encode_tree_workspace_size(const spec_tree *tree, const uint64_t *ro
     return s;
 }
 
-int spec_encode_tree(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
-                     const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap, uint64_t *ends,
-                     void *workspace, size_t workspace_size, uint64_t *total, void *stream) {
+} // extern "C"
+
+// spec_encode_tree (frame_head 0) and spec_encode_tree_frames (4: every record behind its mpx
+// frame head, written by the record's own root writer; the same launches)
+int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
+                             const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap,
+                             uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total, void *stream,
+                             uint32_t frame_head) {
     if (!columns || !rows || !total || !workspace) return SPEC_E_INVALID_ARGUMENT;
     Layout *Lp = new (std::nothrow) Layout();
     if (!Lp) return SPEC_E_INVALID_ARGUMENT;
@@ -636,6 +651,7 @@ int spec_encode_tree(const spec_tree *tree, const void *const *columns, const ui
     B->tmask = (uint64_t *)(ws + w.tmask);
     B->total = total;
     B->err = (uint32_t *)(ws + w.err);
+    B->frame_head = frame_head;
     const TreeDesc *Dd = (const TreeDesc *)(ws + w.desc);
     TreeBufs *Bd = (TreeBufs *)(ws + w.bufs);
     // the generated writers and size passes (jit.cpp) for message tables, else the run-time row kernels
@@ -705,7 +721,7 @@ int spec_encode_tree(const spec_tree *tree, const void *const *columns, const ui
     if (ok) {
         if (n) {
             ok = launch_scan(B->size[0], n, nullptr, B->offsets, nullptr, (uint64_t *)(ws + w.scan), total, B->err,
-                             st) == 0;
+                             st, frame_head) == 0;
         } else {
             ok = hipMemsetAsync(total, 0, sizeof(uint64_t), st) == hipSuccess;
         }
@@ -762,6 +778,25 @@ int spec_encode_tree(const spec_tree *tree, const void *const *columns, const ui
         return SPEC_E_HIP;
     }
     return SPEC_OK;
+}
+
+extern "C" {
+
+int spec_encode_tree(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
+                     const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap, uint64_t *ends,
+                     void *workspace, size_t workspace_size, uint64_t *total, void *stream) {
+    return encode_tree_passes(tree, columns, heaps, heap_lens, rows, out, out_cap, ends, workspace, workspace_size,
+                              total, stream, 0);
+}
+
+// spec_encode_tree with every record behind its mpx frame head (mpx/conn_writer.go:84-97): the
+// bytes of spec_frames_write over spec_encode_tree's stream, from the encoder's own launches
+int spec_encode_tree_frames(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
+                            const uint64_t *heap_lens, const uint64_t *rows, uint8_t *frames, uint64_t frames_cap,
+                            uint64_t *frame_ends, void *workspace, size_t workspace_size, uint64_t *total,
+                            void *stream) {
+    return encode_tree_passes(tree, columns, heaps, heap_lens, rows, frames, frames_cap, frame_ends, workspace,
+                              workspace_size, total, stream, 4);
 }
 
 } // extern "C"

@@ -95,6 +95,11 @@ struct TreeBufs {
     uint32_t *err;
     uint32_t *tblk;  // encode, record-tile writer: per record, the offsets of its field blocks (jit.cpp gen_tile)
     uint64_t *tmask; // encode, record-tile writer: per record, its present direct fields
+    // encode: 0, or 4 (spec_encode_tree_frames): every record behind its mpx frame head.  offsets[]
+    // are then the MESSAGE starts (the scan counts size + 4 per record), so child rows keep their
+    // absolute positions and only the root writers know the head: the u32 big-endian size[0][row]
+    // at start - 4, the first append of the record's own emitter
+    uint32_t frame_head;
 };
 
 __device__ __forceinline__ uint64_t grid_stride() { return (uint64_t)gridDim.x * blockDim.x; }

@@ -140,7 +140,7 @@ class NestedEncoder:
         return hp, hl
 
     def encode(self, outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out=None, ends=None,
-               cuda_stream=None):
+               cuda_stream=None, *, _fn="spec_encode_nested"):
         """outer_cols: one tensor per outer field (None for the list field); item_begin: int32/uint32
         [n+1]; writes out/ends when given, always self.total."""
         ws = _lib.lib().spec_encode_nested_workspace_size_items(self.n, nitems)
@@ -149,12 +149,20 @@ class NestedEncoder:
             self.ws_bytes = ws
         ohp, ohl = self._heaps(self.schema.outer.fields, outer_heaps)
         ihp, ihl = self._heaps(self.schema.item.fields, item_heaps)
-        rc = _lib.lib().spec_encode_nested(
+        rc = getattr(_lib.lib(), _fn)(
             C.byref(self.schema.c), self._ptrs(outer_cols), ohp, ohl, _ptr(item_begin), self._ptrs(item_cols), ihp,
             ihl, nitems, self.n, _ptr(out), out.numel() if out is not None else 0, _ptr(ends), _ptr(self.workspace),
             self.ws_bytes, _ptr(self.total), _stream_handle(cuda_stream))
-        _lib.check(rc, "spec_encode_nested")
+        _lib.check(rc, _fn)
         return self.total
+
+    def encode_frames(self, outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, frames=None,
+                      frame_ends=None, cuda_stream=None):
+        """spec_encode_nested_frames: encode() with every record behind its mpx frame head
+        `[u32 BE size][message]`; writes frames/frame_ends when given, always the framed size
+        (the unframed total + 4n) to self.total."""
+        return self.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, frames, frame_ends,
+                           cuda_stream, _fn="spec_encode_nested_frames")
 
 
 def encode_nested(schema: NestedSchema, outer_cols, outer_heaps, item_begin, item_cols, item_heaps, n: int,
@@ -170,4 +178,21 @@ def encode_nested(schema: NestedSchema, outer_cols, outer_heaps, item_begin, ite
     out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     ends = torch.empty(n, dtype=torch.int64, device=dev)
     enc.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
+    return out[:total], ends
+
+
+def encode_nested_frames(schema: NestedSchema, outer_cols, outer_heaps, item_begin, item_cols, item_heaps, n: int,
+                         cuda_stream=None):
+    """Encode a batch straight to mpx frames -> (frames uint8[total + 4n], frame_ends int64[n]) on the
+    device: the bytes and ends of frames.write_frames(*encode_nested(...)), in the encoder's launches."""
+    dev = item_begin.device
+    enc = NestedEncoder(schema, n, dev)
+    nitems = item_cols[0].shape[0] if item_cols else 0
+    total = int(enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems,
+                                  cuda_stream=cuda_stream).item())
+    if total < 0:
+        raise _lib.SpecError(-1, "spec_encode_nested_frames: encoder error")
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    ends = torch.empty(n, dtype=torch.int64, device=dev)
+    enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
     return out[:total], ends

@@ -446,16 +446,23 @@ class TreeEncoder:
                 hl[c.index] = h.numel()
         return cp, hp, hl, keep
 
-    def encode(self, cols: dict, heaps: dict, out: torch.Tensor | None, ends: torch.Tensor | None, cuda_stream=None):
+    def encode(self, cols: dict, heaps: dict, out: torch.Tensor | None, ends: torch.Tensor | None, cuda_stream=None,
+               *, _fn="spec_encode_tree"):
         cp, hp, hl, keep = self._args(cols, heaps)
-        rc = _lib.lib().spec_encode_tree(C.byref(self.tree.c), cp, hp, hl, self._rows,
+        rc = getattr(_lib.lib(), _fn)(C.byref(self.tree.c), cp, hp, hl, self._rows,
                                          C.c_void_p(out.data_ptr() if out is not None else 0),
                                          out.numel() if out is not None else 0,
                                          C.c_void_p(ends.data_ptr() if ends is not None else 0),
                                          C.c_void_p(self.workspace.data_ptr()), self.ws_bytes,
                                          C.c_void_p(self.total.data_ptr()), _stream_handle(cuda_stream))
-        _lib.check(rc, "spec_encode_tree")
+        _lib.check(rc, _fn)
         return self.total
+
+    def encode_frames(self, cols: dict, heaps: dict, frames: torch.Tensor | None, frame_ends: torch.Tensor | None,
+                      cuda_stream=None):
+        """spec_encode_tree_frames: encode() with every record behind its mpx frame head
+        `[u32 BE size][message]`; self.total is the framed size (the unframed total + 4n)."""
+        return self.encode(cols, heaps, frames, frame_ends, cuda_stream, _fn="spec_encode_tree_frames")
 
 
 def encode_tree(tree: Tree, cols: dict, heaps: dict, n: int, rows=None, cuda_stream=None):
@@ -469,6 +476,21 @@ def encode_tree(tree: Tree, cols: dict, heaps: dict, n: int, rows=None, cuda_str
     out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
     ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
     enc.encode(cols, heaps, out, ends, cuda_stream)
+    return out[:total], ends[:n]
+
+
+def encode_tree_frames(tree: Tree, cols: dict, heaps: dict, n: int, rows=None, cuda_stream=None):
+    """Encode a batch straight to mpx frames -> (frames uint8 [total + 4n], frame_ends int64 [n]) on
+    the device: the bytes and ends of frames.write_frames(*encode_tree(...)), in the encoder's launches."""
+    rows = rows if rows is not None else tree_rows(tree, n, cols)
+    some = next(v for v in cols.values() if v is not None)
+    enc = TreeEncoder(tree, rows, some.device)
+    total = int(enc.encode_frames(cols, heaps, None, None, cuda_stream).item())
+    if total < 0:
+        raise _lib.SpecError(-1, "spec_encode_tree_frames: encoder error")
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
+    ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
+    enc.encode_frames(cols, heaps, out, ends, cuda_stream)
     return out[:total], ends[:n]
 
 
@@ -509,4 +531,4 @@ def pkg1_tree(max_depth: int = 2) -> Tree:
 
 __all__ = ["Struct", "Message", "ListOf", "Tree", "TreeDecoder", "TreeEncoder", "TreeColumns", "decode_tree",
            "decode_values",
-           "encode_tree", "tree_rows", "pkg1_message", "pkg1_tree", "WIDTH"]
+           "encode_tree", "encode_tree_frames", "tree_rows", "pkg1_message", "pkg1_tree", "WIDTH"]
