@@ -38,7 +38,9 @@ extern "C" {
  *   1  rounds 1-4: SPEC_MAX_FIELDS 64, SPEC_TREE_MAX_FIELDS 256 (spec_schema 260 B, spec_tree 2052 B);
  *   2  SPEC_MAX_FIELDS / SPEC_NESTED_MAX_FIELDS / SPEC_TREE_MAX_FIELDS 1024: spec_schema 4100 B,
  *      spec_nested_schema.item at offset 4100, spec_tree 8196 B; spec_struct_size / _offset added;
- *      spec_lz4_state.reserved became content_checksum (same layout); spec_lz4_content added. */
+ *      spec_lz4_state.reserved became content_checksum (same layout); spec_lz4_content added;
+ *      later, with no struct changed: spec_lz4_frame_bound, spec_lz4_compress_workspace_size,
+ *      spec_lz4_compress_frame and the SPEC_LZ4_OPEN / _CLOSE / _CONTENT_CHECKSUM flags. */
 #define SPEC_AMD_ABI_VERSION 2
 /* Fields of a flat schema.  Schemas of up to 64 fields run the schema-specialised kernels; wider
  * ones decode in chunks of 64 fields (the generic kernel once per chunk, each getter against the
@@ -548,6 +550,35 @@ typedef struct spec_lz4_content {
 } spec_lz4_content;
 int spec_lz4_content_update(spec_lz4_content *content, const uint8_t *data, uint64_t len, void *stream);
 int spec_lz4_content_digest(const spec_lz4_content *content, uint32_t *digest, void *stream);
+/* The send half (mpx/conn_writer.go:42-56: lz4.NewWriter + BlockSizeOption(Block256Kb)).
+ * spec_lz4_compress_frame (DEVICE) is ONE Write + Flush of that writer: data[0, len) (device, any
+ * alignment) is cut into blocks of block_max (64 KiB, 256 KiB, 1 MiB or 4 MiB; the last may be
+ * partial), every block compressed on its own, and out[0, *total) (device, any alignment) holds
+ *   - with SPEC_LZ4_OPEN the 7-byte frame header (magic, FLG 0x60 | content checksum bit, BD,
+ *     header checksum byte);
+ *   - per block a u32 LE size word and the payload; a block that compression does not make
+ *     smaller is stored raw, bit 31 of its word set (no block checksums: mpx leaves them off);
+ *   - with SPEC_LZ4_CLOSE the end mark u32 0, and with SPEC_LZ4_CONTENT_CHECKSUM as well
+ *     *content_digest (DEVICE uint32, what spec_lz4_content_digest wrote: no host read needed).
+ * A frame may span any number of calls, OPEN on the first and CLOSE on the last, with the same
+ * CONTENT_CHECKSUM on both; len == 0 writes the header and / or the trailer, or nothing.
+ * *total (device uint64) = bytes written; nothing outside out[0, *total) is written.
+ * spec_lz4_frame_bound (HOST) is the size with every block stored (0: invalid arguments);
+ * out_cap below it is SPEC_E_CAPACITY before any launch.  Every compressed block obeys the LZ4
+ * block format's end rules (the last 5 bytes literals, the last match at least 12 bytes before the
+ * end, offsets 1..65535 inside the block); the same input gives the same bytes on every run;
+ * the bytes pierrec's compressor would choose are not reproduced.  Asynchronous, no
+ * host synchronisation.  SPEC_E_INVALID_ARGUMENT: unknown flag bits, a bad block_max, a NULL
+ * pointer that is needed, CLOSE with CONTENT_CHECKSUM and no digest; SPEC_E_TOO_LARGE: len >=
+ * 4 GiB; every check comes before any HIP call. */
+#define SPEC_LZ4_OPEN 1u             /* write the frame header first */
+#define SPEC_LZ4_CLOSE 2u            /* end mark after the blocks */
+#define SPEC_LZ4_CONTENT_CHECKSUM 4u /* the frame carries a content checksum (header flag; with CLOSE, the checksum) */
+uint64_t spec_lz4_frame_bound(uint64_t len, uint32_t block_max, uint32_t flags);
+size_t spec_lz4_compress_workspace_size(uint64_t len, uint32_t block_max);
+int spec_lz4_compress_frame(const uint8_t *data, uint64_t len, uint32_t block_max, uint32_t flags,
+                            const uint32_t *content_digest, uint8_t *out, uint64_t out_cap, uint64_t *total,
+                            void *workspace, size_t workspace_size, void *stream);
 
 /* ---- host pipeline (the path starts and ends in HOST memory: mpx connection buffers) ----
  * spec_host_decoder decodes a batch held in pinned host memory (spec_host_alloc) into a pinned

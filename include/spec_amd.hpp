@@ -279,6 +279,70 @@ inline Frames WriteFrames(const Batch &b, Stream &s) {
     return f;
 }
 
+// lz4.Writer as mpx wraps a connection in it (conn_writer.go:42-56: lz4.NewWriter +
+// BlockSizeOption(Block256Kb)): one LZ4 frame, a flush segment per Write, the end mark and the
+// content checksum with Close.  Everything stays on the device and is asynchronous: the bytes
+// of a call are segment.bytes[0, *segment.total), the checksum is kept in a device
+// spec_lz4_content and handed to the closing call as a device pointer.
+struct Lz4Segment {
+    DeviceBuffer bytes; // the bound of the call; [0, Size()) is written
+    DeviceBuffer total; // device uint64
+    uint64_t Size(Stream &s) const {
+        uint64_t t = 0;
+        total.CopyTo(&t, 8, s);
+        s.Sync();
+        return t;
+    }
+};
+
+class Lz4FrameWriter {
+  public:
+    explicit Lz4FrameWriter(Stream &s, uint32_t block_max = 256u << 10, bool content_checksum = true)
+        : block_max_(block_max), content_(content_checksum) {
+        if (content_) {
+            state_ = DeviceBuffer::From(std::vector<uint8_t>(sizeof(spec_lz4_content), 0), s);
+            digest_ = DeviceBuffer(4);
+        }
+    }
+    // one Write + Flush: data[0, len) on the device
+    Lz4Segment Write(const void *data, uint64_t len, Stream &s) {
+        if (content_)
+            Check(spec_lz4_content_update((spec_lz4_content *)state_.data(), (const uint8_t *)data, len, s.get()),
+                  "spec_lz4_content_update");
+        return Call((const uint8_t *)data, len, 0, s);
+    }
+    Lz4Segment Close(Stream &s) {
+        if (content_)
+            Check(spec_lz4_content_digest((const spec_lz4_content *)state_.data(), (uint32_t *)digest_.data(), s.get()),
+                  "spec_lz4_content_digest");
+        return Call(nullptr, 0, SPEC_LZ4_CLOSE, s);
+    }
+
+  private:
+    Lz4Segment Call(const uint8_t *data, uint64_t len, uint32_t flags, Stream &s) {
+        flags |= (opened_ ? 0u : SPEC_LZ4_OPEN) | (content_ ? SPEC_LZ4_CONTENT_CHECKSUM : 0u);
+        const uint64_t bound = spec_lz4_frame_bound(len, block_max_, flags);
+        if (!bound && (len || flags != 0)) throw Error(SPEC_E_INVALID_ARGUMENT, "spec_lz4_frame_bound");
+        const size_t ws = spec_lz4_compress_workspace_size(len, block_max_);
+        if (ws > ws_.size()) {
+            s.Sync(); // earlier calls may still use the smaller one
+            ws_ = DeviceBuffer(ws);
+        }
+        Lz4Segment seg;
+        seg.bytes = DeviceBuffer(bound + 1);
+        seg.total = DeviceBuffer(8);
+        Check(spec_lz4_compress_frame(data, len, block_max_, flags, (const uint32_t *)digest_.data(),
+                                      (uint8_t *)seg.bytes.data(), bound, (uint64_t *)seg.total.data(), ws_.data(),
+                                      ws_.size(), s.get()),
+              "spec_lz4_compress_frame");
+        opened_ = true;
+        return seg;
+    }
+    uint32_t block_max_;
+    bool content_, opened_ = false;
+    DeviceBuffer state_, digest_, ws_;
+};
+
 // Pinned host memory (hipHostMalloc): what an mpx connection reads frames into.
 class PinnedBuffer {
   public:

@@ -9,6 +9,7 @@ from ._lib import LIB_PATH, SpecError, header_symbols, lib, set_jit
 from .batch import (PARSE_LIST, PARSE_MESSAGE, PARSE_VALUE, Columns, Decoder, Encoder, alloc_columns, decode_flat,
                     decode_flat_errors, encode_flat, encode_flat_frames, parse_messages)
 from . import lz4
+from .lz4 import Lz4Writer, compress_frame, frame_bound
 from .frames import decode_frames, frames_index, frames_index_device, make_frames, make_frames_device, write_frames
 from .pipeline import HostDecoder
 from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, encode_nested,
@@ -18,7 +19,7 @@ from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, Tree
                    encode_tree, encode_tree_frames, pkg1_message, pkg1_tree, tree_rows)
 
 __all__ = [
-    "HostDecoder", "decode_frames", "frames_index", "frames_index_device", "make_frames", "make_frames_device", "write_frames", "LIB_PATH", "SpecError", "header_symbols", "lib", "set_jit", "Columns", "Decoder", "Encoder", "alloc_columns",
+    "HostDecoder", "decode_frames", "frames_index", "frames_index_device", "make_frames", "make_frames_device", "write_frames", "Lz4Writer", "compress_frame", "frame_bound", "LIB_PATH", "SpecError", "header_symbols", "lib", "set_jit", "Columns", "Decoder", "Encoder", "alloc_columns",
     "decode_flat", "decode_flat_errors", "encode_flat", "encode_flat_frames", "parse_messages", "PARSE_MESSAGE", "PARSE_LIST", "PARSE_VALUE",
     "FLAT16", "Field", "Kind", "Schema",
     "NESTED", "NestedSchema", "NestedColumns", "NestedDecoder", "NestedEncoder", "decode_nested",

@@ -195,6 +195,12 @@ def _declare(L):
     L.spec_lz4_pack.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_size_t, vp]
     L.spec_lz4_content_update.argtypes = [vp, vp, C.c_uint64, vp]
     L.spec_lz4_content_digest.argtypes = [vp, vp, vp]
+    L.spec_lz4_frame_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    L.spec_lz4_frame_bound.restype = C.c_uint64
+    L.spec_lz4_compress_workspace_size.argtypes = [C.c_uint64, C.c_uint32]
+    L.spec_lz4_compress_workspace_size.restype = C.c_size_t
+    L.spec_lz4_compress_frame.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, vp, vp,
+                                          C.c_size_t, vp]
     L.spec_frames_write.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
     L.spec_tree_layout.argtypes = [C.POINTER(SpecTree), C.POINTER(SpecTreeTable), C.POINTER(C.c_uint32),
                                    C.POINTER(SpecTreeColumn), C.POINTER(C.c_uint32)]

@@ -1,5 +1,5 @@
 // lz4_host.cpp — spec_lz4_frame_blocks (host walk of LZ4 frame headers and block size words)
-// and the C-ABI entry points of the device LZ4 path (lz4_device.hip).
+// and the C-ABI entry points of the device LZ4 path (lz4_device.hip, lz4_compress.hip).
 //
 // What pierrec/lz4/v4's Reader checks before it decodes a block (mpx/conn_reader.go:53-62 wraps
 // the connection in lz4.NewReader), restated from the LZ4 frame format: magic 0x184D2204 (and
@@ -10,6 +10,7 @@
 
 #include <string.h>
 
+#include "lz4_compress_core.hpp"
 #include "spec_internal.hpp"
 
 namespace {
@@ -172,6 +173,39 @@ int spec_lz4_pack(const uint8_t *slots, uint64_t slot_bytes, const uint32_t *siz
     if (workspace_size < spec_lz4_pack_workspace_size(nblocks)) return SPEC_E_WORKSPACE;
     if (spec::launch_lz4_pack(slots, slot_bytes, sizes, nblocks, out, out_cap, (uint64_t *)workspace, total,
                               (hipStream_t)stream))
+        return SPEC_E_HIP;
+    return SPEC_OK;
+}
+
+// ---- the send half: spec_lz4_compress_frame (lz4_compress.hip) ----
+uint64_t spec_lz4_frame_bound(uint64_t len, uint32_t block_max, uint32_t flags) {
+    if (spec::lz4c::block_code(block_max) < 0 || !spec::lz4c::flags_ok(flags) || len >= (1ull << 32)) return 0;
+    return spec::lz4c::frame_bound(len, block_max, flags);
+}
+
+size_t spec_lz4_compress_workspace_size(uint64_t len, uint32_t block_max) {
+    if (spec::lz4c::block_code(block_max) < 0 || len >= (1ull << 32)) return 0;
+    return (size_t)spec::lz4c::workspace_layout(len, block_max).bytes;
+}
+
+int spec_lz4_compress_frame(const uint8_t *data, uint64_t len, uint32_t block_max, uint32_t flags,
+                            const uint32_t *content_digest, uint8_t *out, uint64_t out_cap, uint64_t *total,
+                            void *workspace, size_t workspace_size, void *stream) {
+    namespace Z = spec::lz4c;
+    if (!Z::flags_ok(flags) || Z::block_code(block_max) < 0 || !total) return SPEC_E_INVALID_ARGUMENT;
+    if (len && (!data || !out || !workspace)) return SPEC_E_INVALID_ARGUMENT;
+    if ((flags & Z::FLAG_CLOSE) && (flags & Z::FLAG_CONTENT) && !content_digest) return SPEC_E_INVALID_ARGUMENT;
+    if (len >= (1ull << 32)) return SPEC_E_TOO_LARGE;
+    const uint64_t bound = Z::frame_bound(len, block_max, flags);
+    if (bound && !out) return SPEC_E_INVALID_ARGUMENT;
+    if (out_cap < bound) return SPEC_E_CAPACITY;
+    if (len && workspace_size < Z::workspace_layout(len, block_max).bytes) return SPEC_E_WORKSPACE;
+    // the header is one of eight: magic, FLG, BD and the descriptor's checksum byte
+    const uint8_t desc[2] = {Z::header_flg(flags), (uint8_t)(Z::block_code(block_max) << 4)};
+    const uint64_t header = (uint64_t)Z::FRAME_MAGIC | ((uint64_t)desc[0] << 32) | ((uint64_t)desc[1] << 40) |
+                            ((uint64_t)((xxh32(desc, 2, 0) >> 8) & 0xff) << 48);
+    if (spec::launch_lz4_compress_frame(data, len, block_max, flags, header, content_digest, out, total, workspace,
+                                        (hipStream_t)stream))
         return SPEC_E_HIP;
     return SPEC_OK;
 }

@@ -62,6 +62,11 @@ int launch_lz4_pack(const uint8_t *slots, uint64_t slot, const uint32_t *sizes, 
                     uint64_t out_cap, uint64_t *offsets, uint64_t *total, hipStream_t stream);
 // xxHash32 of the frame content: data != null appends data[0, len); digest != null writes the digest
 int launch_lz4_content(spec_lz4_content *c, const uint8_t *data, uint64_t len, uint32_t *digest, hipStream_t stream);
+// lz4_compress.hip: data[0, len) as blocks of an LZ4 frame at out (header: the 7 header bytes,
+// little-endian, written with SPEC_LZ4_OPEN); the workspace is lz4c::workspace_layout(len, block_max)
+int launch_lz4_compress_frame(const uint8_t *data, uint64_t len, uint32_t block_max, uint32_t flags, uint64_t header,
+                              const uint32_t *content_digest, uint8_t *out, uint64_t *total, void *workspace,
+                              hipStream_t stream);
 // frames_write.hip
 int launch_frames_write(const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends, uint64_t n,
                         uint8_t *frames, uint64_t *frame_ends, hipStream_t stream);

@@ -5,6 +5,10 @@ LZ4 frame of independent 256 KiB blocks per connection, pierrec/lz4/v4).
 one u32 per block, header/block checksums verified); `decompress` runs every block on the GPU
 (spec_lz4_decompress: one wave per block) and packs the blocks back to back
 (spec_lz4_pack) — the decompressed mpx frames then go to frames_index_device + decode_frames.
+
+The send half: `compress_frame` is one Write + Flush of mpx's lz4.Writer on the GPU
+(spec_lz4_compress_frame: a wave per block), `Lz4Writer` a frame over any number of such calls
+with its content checksum kept on the device.
 """
 from __future__ import annotations
 
@@ -52,10 +56,14 @@ class ContentChecksum:
                                                       data.numel(), _stream_handle(cuda_stream)),
                    "spec_lz4_content_update")
 
-    def digest(self, cuda_stream=None) -> int:
+    def digest_device(self, cuda_stream=None) -> torch.Tensor:
+        """The digest as a device int32 tensor of one element (no host read)."""
         _lib.check(_lib.lib().spec_lz4_content_digest(_ptr(self.state), _ptr(self.out), _stream_handle(cuda_stream)),
                    "spec_lz4_content_digest")
-        return int(self.out.item()) & 0xFFFFFFFF
+        return self.out
+
+    def digest(self, cuda_stream=None) -> int:
+        return int(self.digest_device(cuda_stream).item()) & 0xFFFFFFFF
 
 
 def frame_blocks(buf: np.ndarray, state: Lz4State | None = None, cap: int | None = None):
@@ -105,3 +113,85 @@ def decompress(src: torch.Tensor, blocks: np.ndarray, block_max: int, cuda_strea
     if t < 0:
         raise _lib.SpecError(-6, "spec_lz4_decompress: corrupt block")
     return out[:t], sizes[:nb].view(torch.int32), status[:nb]
+
+
+OPEN, CLOSE, CONTENT_CHECKSUM = 1, 2, 4  # SPEC_LZ4_OPEN / _CLOSE / _CONTENT_CHECKSUM
+
+
+def frame_bound(n: int, block_max: int = 256 << 10, flags: int = OPEN) -> int:
+    """spec_lz4_frame_bound: the bytes one compress_frame call may write (every block stored)."""
+    b = int(_lib.lib().spec_lz4_frame_bound(n, block_max, flags))
+    if b == 0 and (n or flags & (OPEN | CLOSE)):
+        raise _lib.SpecError(-1, "spec_lz4_frame_bound")
+    return b
+
+
+def compress_frame_into(data: torch.Tensor, out: torch.Tensor, total: torch.Tensor, block_max: int = 256 << 10,
+                        flags: int = OPEN, digest: torch.Tensor | None = None, workspace: torch.Tensor | None = None,
+                        cuda_stream=None):
+    """spec_lz4_compress_frame as it is: out (uint8) gets the bytes, total (int64 [1]) their number; nothing
+    is read back.  digest: a device int32 [1] (ContentChecksum.digest_device) for a checksummed CLOSE."""
+    _check_dev(data, "data", torch.uint8)
+    L = _lib.lib()
+    n = data.numel()
+    wsb = L.spec_lz4_compress_workspace_size(n, block_max)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 16), dtype=torch.uint8, device=data.device)
+    rc = L.spec_lz4_compress_frame(_ptr(data) if n else None, n, block_max, flags,
+                                   _ptr(digest) if digest is not None else None, _ptr(out) if out.numel() else None,
+                                   out.numel(), _ptr(total), _ptr(workspace), workspace.numel(),
+                                   _stream_handle(cuda_stream))
+    _lib.check(rc, "spec_lz4_compress_frame")
+    return workspace
+
+
+def compress_frame(data: torch.Tensor, block_max: int = 256 << 10, open: bool = True, close: bool = False,
+                   content: ContentChecksum | None = None, cuda_stream=None) -> torch.Tensor:
+    """One Write + Flush of mpx's LZ4 writer (mpx/conn_writer.go:42-56) over `data` (uint8, device):
+    -> the bytes it puts on the wire (uint8 device tensor): the frame header with `open`, data's blocks
+    of block_max each compressed on its own or stored, the end mark with `close`.  `content`: the
+    frame carries a content checksum (the same on every call of the frame); it must already hold
+    everything the frame contains, this call's data included, when `close` is set."""
+    flags = (OPEN if open else 0) | (CLOSE if close else 0) | (CONTENT_CHECKSUM if content is not None else 0)
+    dev = data.device
+    out = torch.empty(frame_bound(data.numel(), block_max, flags), dtype=torch.uint8, device=dev)
+    total = torch.zeros(1, dtype=torch.int64, device=dev)
+    digest = content.digest_device(cuda_stream) if (content is not None and close) else None
+    ws = compress_frame_into(data, out, total, block_max, flags, digest, cuda_stream=cuda_stream)
+    if cuda_stream is not None:
+        torch.cuda.synchronize(dev)  # total and the workspace belong to that stream
+    del ws
+    return out[: int(total.item())]
+
+
+class Lz4Writer:
+    """lz4.Writer as mpx uses it, on the device: write(data) is one Write + Flush (a flush segment
+    of the connection's single frame), close() the end mark and, with content_checksum, the
+    checksum of everything written — kept on the device (ContentChecksum) and handed to the closing
+    call as a device pointer."""
+
+    def __init__(self, block_max: int = 256 << 10, content_checksum: bool = True, device="cuda"):
+        self.block_max = block_max
+        self.device = torch.device(device)
+        self.content = ContentChecksum(device) if content_checksum else None
+        self.opened = False
+        self.closed = False
+
+    def write(self, data: torch.Tensor, cuda_stream=None) -> torch.Tensor:
+        if self.closed:
+            raise ValueError("Lz4Writer: write after close")
+        if self.content is not None:
+            self.content.update(data, cuda_stream)
+        out = compress_frame(data, self.block_max, open=not self.opened, close=False, content=self.content,
+                             cuda_stream=cuda_stream)
+        self.opened = True
+        return out
+
+    def close(self, cuda_stream=None) -> torch.Tensor:
+        if self.closed:
+            raise ValueError("Lz4Writer: closed twice")
+        empty = torch.zeros(0, dtype=torch.uint8, device=self.device)
+        out = compress_frame(empty, self.block_max, open=not self.opened, close=True, content=self.content,
+                             cuda_stream=cuda_stream)
+        self.opened = self.closed = True
+        return out

@@ -236,3 +236,38 @@ def bench_wide_schemas():
     tags40 = [int(t) for t in np.random.default_rng(3).permutation(np.arange(1, 41))]
     return {"wide40": Schema([(t, kinds[i % 15]) for i, t in enumerate(tags40)]),
             "big16": Schema([(256 + 37 * i, kinds[i % 15]) for i in range(16)])}
+
+
+# ---- byte streams for the LZ4 paths (tests/test_gpu_lz4_compress.py, tools/bench_lz4_compress.py) ----
+LZ4_KINDS = ("text", "random", "mixed", "zeros", "period3", "period200", "records", "chunks", "longlit")
+
+
+def lz4_chunks(rng, n, lit, rep):
+    """random runs of `lit` bytes, each followed by `rep` bytes copied from earlier output"""
+    out = bytearray()
+    while len(out) < n:
+        out += rng.integers(0, 256, lit, dtype=np.uint8).tobytes()
+        src = int(rng.integers(0, max(1, len(out) - rep)))
+        out += out[src:src + rep]
+    return np.frombuffer(bytes(out[:n]), np.uint8)
+
+
+def lz4_data(kind: str, n: int) -> np.ndarray:
+    """n bytes of one of LZ4_KINDS: from nothing to match (random) to one match a block (zeros),
+    short and long periods, many short sequences (records), matches up to a block back (chunks),
+    literal runs of kilobytes (longlit)."""
+    rng = np.random.default_rng(sum(kind.encode()) % 1000)
+    d = {
+        "text": lambda: np.frombuffer((b"spec message field table trailer " * (n // 33 + 1))[:n], np.uint8),
+        "random": lambda: rng.integers(0, 256, n, dtype=np.uint8),
+        "mixed": lambda: np.concatenate([rng.integers(0, 6, n // 2, dtype=np.uint8),
+                                         rng.integers(0, 256, n - n // 2, dtype=np.uint8)]),
+        "zeros": lambda: np.zeros(n, np.uint8),
+        "period3": lambda: np.frombuffer((b"abc" * (n // 3 + 1))[:n], np.uint8),
+        "period200": lambda: np.tile(rng.integers(0, 256, 200, dtype=np.uint8), n // 200 + 1)[:n],
+        "records": lambda: np.tile(np.frombuffer(b"".join(bytes([7, i % 13, 0, 0]) + rng.integers(0, 256, 9, dtype=np.uint8)
+                                                          .tobytes() for i in range(64)), np.uint8), n // 832 + 1)[:n],
+        "chunks": lambda: lz4_chunks(rng, n, 300, 700),
+        "longlit": lambda: lz4_chunks(rng, n, 9000, 3000),
+    }[kind]()
+    return np.ascontiguousarray(d).copy()
