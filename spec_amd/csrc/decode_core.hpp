@@ -1025,82 +1025,8 @@ __device__ __forceinline__ Group make_group(const DecodeArgs &a, uint64_t base, 
     return make_group(a.n, base, lo, hi, slab);
 }
 
-// Persistent waves: wave w of the grid decodes groups w, w + W, w + 2W, ... (W = waves in the
-// grid, sized by the launcher to what the CUs hold at once).  Per group:
-//   wait for its DMA -> fast_prepare (trailer, table, all field windows into registers) and
-//   the generic path for any rejected record -> the slab is free: issue the NEXT group's DMA
-//   -> decode + store this group from registers while that DMA is in flight.
-template <class Spec, bool ERR = false>
-__device__ __forceinline__ void decode_flat_body(const DecodeArgs &a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int nw = blockDim.x >> 6;
-    const int wave = threadIdx.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const uint64_t ngroups = (a.n - a.r0 + 63) / 64;
-    const uint64_t stride = (uint64_t)gridDim.x * nw;
-    uint64_t g = (uint64_t)blockIdx.x * nw + wave;
-    if (g >= ngroups) return;
-    uint8_t *slab = smem + wave * a.slab;
-    __amdgpu_buffer_rsrc_t rsrc =
-        uniform_rsrc(a.stream, a.stream_len);
-
-    uint64_t lo, hi;
-    load_group_ends(a, a.r0 + g * 64, lane, lo, hi);
-    Group cur = make_group(a, a.r0 + g * 64, lane, lo, hi, a.slab);
-    if (cur.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, cur.st, lane);
-    // the next group's ends are always one iteration ahead
-    uint64_t gn = g + stride, nlo = 0, nhi = 0;
-    if (gn < ngroups) load_group_ends(a, a.r0 + gn * 64, lane, nlo, nhi);
-
-    while (true) {
-        const uint64_t base = a.r0 + g * 64;
-        const uint64_t r = base + lane;
-        const bool valid = r < a.n;
-        const bool has_next = gn < ngroups;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this group's DMA, the next group's ends
-        const Group nxt = make_group(a, has_next ? a.r0 + gn * 64 : base, lane, nlo, nhi, a.slab);
-        const uint64_t g2 = gn + stride;
-        uint64_t lo2 = 0, hi2 = 0;
-
-        if (cur.in_lds) {
-            stage_fix_tail(rsrc, slab + SLAB_GUARD, cur.st, a.stream_len, lane);
-            LdsSrc s{(lds_u8 *)slab};
-            const int rs = cur.rs(), re = cur.re();
-            const long long to_stream = cur.to_stream();
-            if constexpr (Spec::N > 0) {
-                FastRec<Spec> fr;
-                bool fast = valid && fast_prepare<Spec>(s, rs, re, fr);
-                if (valid && !fast) decode_record_generic(s, rs, re, r, a.f, to_stream);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // every LDS read of this group done
-                if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
-                if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
-                if (fast) fast_finish<Spec, ERR>(fr, r, a.f, to_stream);
-            } else {
-                if (valid) decode_record_generic(s, rs, re, r, a.f, to_stream);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
-                if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
-            }
-        } else {
-            if (has_next && nxt.in_lds) stage_issue<STREAM_AUX>(rsrc, slab + SLAB_GUARD, nxt.st, lane);
-            if (g2 < ngroups) load_group_ends(a, a.r0 + g2 * 64, lane, lo2, hi2);
-            if (valid) {
-                GlobalSrc s{a.stream, a.stream_len};
-                decode_record_generic(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
-            }
-        }
-        if (!has_next) break;
-        g = gn;
-        gn = g2;
-        cur = nxt;
-        nlo = lo2;
-        nhi = hi2;
-    }
-}
-
-// One group per wave (the default grid): stage, decode, done.  Same steps as one iteration of
-// decode_flat_body without the hand-off to a next group, so nothing fences the fast path's
-// LDS reads from its decode and stores.
+// One group per wave: stage, decode, done.  ERR: the variant that also writes the per-record
+// field error masks (a.f.errmask, spec_decode_flat_errors).
 template <class Spec, bool ERR = false>
 __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1156,7 +1082,7 @@ __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
 // writes the status — or, where either half needs it, runs the generic path over the whole
 // record (it rewrites every column).  Same LDS per 64 records, twice the waves: one wave's LDS
 // and memory latency overlaps the other's decode.  ERR: every wave's mask bits, OR-ed by wave 0.
-// P waves per group in general (P parts of the fields; build-time A/B, jit.cpp SPEC_AB_FLAT_WAVES).
+// P waves per group in general (P parts of the fields; jit.cpp FLAT_WAVES).
 template <class Spec, bool ERR = false, int P = 2>
 __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1217,44 +1143,18 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     }
 }
 
-// Kernel entry: PERSIST selects the persistent, software-pipelined loop; ERR the variant that
-// also writes the per-record field error masks (a.f.errmask, spec_decode_flat_errors).
-template <bool PERSIST, class Spec, bool ERR = false>
-__device__ __forceinline__ void decode_flat_entry(const DecodeArgs &a) {
-    if constexpr (PERSIST)
-        decode_flat_body<Spec, ERR>(a);
-    else
-        decode_flat_once<Spec, ERR>(a);
-}
-
-bool xcd_swizzle_decode(); // XCD-aware block order, default on; build-time SPEC_AB_NOXCD off (decode_flat.hip)
-
-// Launch shape of the flat decode: per-wave slab, waves per block, grid.
+// Launch shape of the flat decode's wave-per-group kernels: per-wave slab, grid.
 struct DecodeLaunch {
-    uint32_t slab;   // bytes per wave
-    unsigned wpb;    // waves per block
+    uint32_t slab; // bytes per wave = dynamic LDS per block
     unsigned blocks;
-    size_t lds;      // dynamic LDS per block
 };
 
-// One group per wave (default): `wpb` waves per block (1 packs the most slabs per CU: LDS
-// is the occupancy limit).  Persistent: as many blocks as the CUs hold at once, each wave
-// looping over groups with the next group's DMA overlapping this group's decode.
-__host__ inline DecodeLaunch decode_launch(uint64_t nrec, double avg_record, int cus, bool persistent, unsigned wpb) {
+// One group per wave, one wave per block (packs the most slabs per CU: LDS is the occupancy
+// limit), the grid rounded up to 8 equal XCD shares (the kernels' a.xcd block order).
+__host__ inline DecodeLaunch decode_launch(uint64_t nrec, double avg_record) {
     DecodeLaunch L;
     L.slab = decode_slab_bytes(avg_record);
-    L.wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
-    const uint64_t groups = (nrec + 63) / 64;
-    uint64_t need = (groups + L.wpb - 1) / L.wpb;
-    if (xcd_swizzle_decode() && !persistent) need = (need + 7) / 8 * 8; // 8 equal XCD shares
-    if (persistent) {
-        int per_cu = L.slab > 0 ? (int)((160 * 1024) / (L.wpb * L.slab)) : 8;
-        per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-        const uint64_t cap = (uint64_t)cus * per_cu;
-        need = need < cap ? need : cap;
-    }
-    L.blocks = (unsigned)need;
-    L.lds = (size_t)L.wpb * L.slab;
+    L.blocks = (unsigned)(((nrec + 63) / 64 + 7) / 8 * 8);
     return L;
 }
 

@@ -1,6 +1,6 @@
 // decode_nested_core.hpp — device code of the list<message> decoder (BASELINE config 4),
 // shared by the precompiled kernels (decode_nested.hip, run-time schema) and the
-// schema-specialised one-pass kernel jit.cpp compiles with hiprtc.
+// schema-specialised decode kernels jit.cpp compiles with hiprtc.
 //
 // Per record the reference runs (generated reader, internal/lang/generator/message.go:154-162):
 //   m, err := spec.OpenMessageErr(b)                       internal/types/msg.go:43-55
@@ -23,13 +23,9 @@
 // schema-specialised fast path (decode_core.hpp) when the kernel has one (OSpec / ISpec), the
 // generic path otherwise.
 //
-// Where the group's first item goes:
-//   * two-pass (spec_decode_nested_index + spec_decode_nested): a count kernel and a scan
-//     kernel write every group's item offset first;
-//   * one pass (spec_decode_nested_onepass): groups are taken in order from an atomic ticket
-//     and publish their item count, then their inclusive prefix, in a per-group state word;
-//     a group finds its offset by looking back over its predecessors' words (decoupled
-//     look-back: a window of 64 predecessors per step, one per lane).
+// Where the group's first item goes: a count kernel and a scan kernel write every group's item
+// offset first (spec_decode_nested_index, then spec_decode_nested; spec_decode_nested_onepass
+// runs both back to back).
 #pragma once
 
 #include "decode_core.hpp"
@@ -92,26 +88,9 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return v;
 }
 
-// Stage one wave's group (records [base, base+64)) into its slab: returns the group; if
+// Stage lanes [l0, l1) of one wave's group (records [base, base+64)) into its slab (a group whose
+// whole span exceeds the slab is staged and decoded in two halves): returns the part; if
 // gr.in_lds the bytes are in LDS when this returns.
-__device__ __forceinline__ Group nested_stage(const NestedArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint8_t *slab,
-                                              uint64_t base, int lane) {
-    uint64_t lo, hi;
-    DecodeArgs d;
-    d.stream = a.stream;
-    d.stream_len = a.stream_len;
-    d.ends = a.ends;
-    d.n = a.n;
-    d.r0 = 0;
-    d.head = 0;
-    load_group_ends(d, base, lane, lo, hi);
-    Group gr = make_group(d, base, lane, lo, hi, a.slab);
-    if (gr.in_lds) stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
-    return gr;
-}
-
-// Lanes [l0, l1) of the group only (a group whose whole span exceeds the slab is staged and
-// decoded in two halves): the part's span, staged into the slab if it fits.
 __device__ __forceinline__ Group nested_stage_part(const NestedArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint8_t *slab,
                                                    uint64_t base, int lane, int l0, int l1) {
     uint64_t lo, hi;
@@ -319,110 +298,18 @@ __device__ __forceinline__ void decode_group_items_ranges(const LdsSrc &s, const
     }
 }
 
-// ---- decoupled look-back (one pass) ------------------------------------------------------
-
-constexpr uint64_t LB_AGG = 1ull << 62;       // word holds the group's own item count
-constexpr uint64_t LB_PRE = 2ull << 62;       // word holds the inclusive prefix (items up to and incl. the group)
-constexpr uint64_t LB_VAL = (1ull << 62) - 1;
-
-__device__ __forceinline__ uint64_t lb_load(const uint64_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void lb_store(uint64_t *p, uint64_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// Publish unit g's item count `agg`, return the items of units [0, g).  Units are blocks of
-// DEC_WAVES groups in block order (workgroups are dispatched in increasing id, so every unit < g
-// is resident or done and will publish: the wait ends).  The window looks back 256 units per
-// round (4 per lane, nearest first); 1,024 per round (16 per lane) measured no faster.
-__device__ __forceinline__ uint64_t lookback(uint64_t *state, uint64_t g, uint64_t agg, int lane) {
-    constexpr int K = 4;
-    if (lane == 0) lb_store(&state[g], (g == 0 ? LB_PRE : LB_AGG) | agg);
-    if (g == 0) return 0;
-    uint64_t excl = 0;
-    long long hi = (long long)g - 1; // window: group hi - (lane + 64 k) on lane `lane`, slot k
-    while (true) {
-        uint64_t v[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const long long j = hi - lane - 64 * k;
-            v[k] = j >= 0 ? lb_load(&state[j]) : LB_PRE; // before group 0: prefix 0
-        }
-        int first = 64 * K; // distance of the nearest inclusive prefix
-        bool wait = false;
-#pragma unroll
-        for (int k = K - 1; k >= 0; k--) {
-            const uint64_t pre = __ballot((v[k] >> 62) == 2);
-            if (pre) first = 64 * k + __builtin_ctzll(pre);
-        }
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const uint64_t none = __ballot((v[k] >> 62) == 0);
-            const int lim = first - 64 * k; // lanes of slot k nearer than `first`, or at it
-            if (lim >= 0 && none & (lim >= 63 ? ~0ull : ((2ull << lim) - 1))) wait = true;
-        }
-        if (wait) { // a nearer group has not published yet
-            __builtin_amdgcn_s_sleep(1);
-            continue;
-        }
-        uint64_t part = 0;
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            if (lane + 64 * k <= first) part += v[k] & LB_VAL;
-        excl += wave_sum64(part);
-        if (first < 64 * K) break;
-        hi -= 64 * K;
-    }
-    if (lane == 0) lb_store(&state[g], LB_PRE | (excl + agg));
-    return excl;
-}
-
-// ONEPASS: the block's groups (one per wave) sum their item totals in LDS (xch); wave 0 publishes
-// the block's total and looks back over the earlier blocks; each wave's first item = the block's
-// base + the totals of the block's earlier waves.  Every wave of the block calls this once (a
-// wave past the batch's end with total 0).
-__device__ __forceinline__ uint64_t onepass_base(const NestedArgs &a, uint32_t total, int lane, uint64_t *xch) {
-    const int wave = threadIdx.x >> 6;
-    if (lane == 0) xch[wave] = total;
-    __syncthreads();
-    uint64_t before = 0, bt = 0;
-#pragma unroll
-    for (int w = 0; w < DEC_WAVES; w++) {
-        const uint64_t t = xch[w];
-        before += w < wave ? t : 0;
-        bt += t;
-    }
-    if (wave == 0) {
-        const uint64_t b = uniform64(lookback(a.group_base, blockIdx.x, bt, lane));
-        if (lane == 0) xch[DEC_WAVES] = b;
-    }
-    __syncthreads();
-    return uniform64(xch[DEC_WAVES] + before);
-}
-
 // Decode a group: outer records (lane = record), then items (item-parallel).  item_base =
-// the group's first item; ONEPASS: item_base is found here by look-back (state = a.group_base).
-template <class OSpec, class ISpec, bool ONEPASS, int U = NESTED_ITEM_U, class Src>
+// the group's first item (a.group_base, from the index kernels).
+template <class OSpec, class ISpec, int U = NESTED_ITEM_U, class Src>
 __device__ __forceinline__ uint32_t nested_group_body(const Src &s, long long rs, long long re, bool valid,
-                                                      uint64_t r, uint64_t g, uint64_t item_base, int lane,
+                                                      uint64_t r, uint64_t item_base, int lane,
                                                       long long to_stream, const NestedArgs &a,
-                                                      uint32_t *rng = nullptr, uint64_t *xch = nullptr) {
+                                                      uint32_t *rng = nullptr) {
     ListInfo li = {0, 0, 0, 0, false};
     if (valid) li = decode_outer<OSpec>(s, rs, re, r, to_stream, a);
     const uint32_t incl = wave_incl_scan(li.count, lane);
     const uint32_t excl = incl - li.count;
     const uint32_t total = __shfl(incl, 63);
-    if constexpr (ONEPASS) {
-        item_base = onepass_base(a, total, lane, xch);
-        if (g == (a.n - 1) / 64 && lane == 0) *a.total = item_base + total;
-    }
     if (valid) {
         a.item_begin[r] = (uint32_t)(item_base + excl);
         if (r == a.n - 1) a.item_begin[a.n] = (uint32_t)(item_base + incl);
@@ -449,83 +336,50 @@ __device__ __forceinline__ uint32_t nested_decode_part(const NestedArgs &a, __am
     const bool valid = r < a.n && lane >= l0 && lane < l1;
     if (gr.in_lds) {
         LdsSrc s{(lds_u8 *)slab};
-        return nested_group_body<OSpec, ISpec, false, U>(s, gr.rs(), gr.re(), valid, r, g, item_base, lane,
-                                                      gr.to_stream(), a,
-                                                      RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
+        return nested_group_body<OSpec, ISpec, U>(s, gr.rs(), gr.re(), valid, r, item_base, lane, gr.to_stream(), a,
+                                                  RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
     }
     GlobalSrc s{a.stream, a.stream_len};
-    return nested_group_body<OSpec, ISpec, false, U>(s, (long long)gr.rec_lo, (long long)gr.rec_hi, valid, r, g,
-                                                  item_base, lane, 0, a);
+    return nested_group_body<OSpec, ISpec, U>(s, (long long)gr.rec_lo, (long long)gr.rec_hi, valid, r, item_base, lane,
+                                              0, a);
 }
 
-// Kernel body for one group per wave.  ONEPASS: group = wave index, a.group_base = one state word
-// per block (zeroed by the launcher); else group = wave index and a.group_base holds the
-// exclusive item offsets from the index kernels.
-template <class OSpec, class ISpec, bool ONEPASS, bool RANGES = false, int U = NESTED_ITEM_U>
+// Kernel body for one group per wave: a.group_base holds the groups' exclusive item offsets
+// from the index kernels.
+template <class OSpec, class ISpec, bool RANGES = false, int U = NESTED_ITEM_U>
 __device__ __forceinline__ void nested_decode_body(const NestedArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint64_t g;
-    if constexpr (ONEPASS) {
-        // group = block order: workgroups are dispatched in increasing id, so every group a
-        // group waits on (a smaller id) is running or done — the lowest running group never waits
-        // (round 4 took a ticket from one global counter: 16 K agent-scope atomics on one address)
-        g = (uint64_t)blockIdx.x * (blockDim.x >> 6) + wave;
-    } else {
-        // blocks are dealt round-robin to the 8 XCDs: with xcd = 1, block b takes the b/8-th slot
-        // of XCD b%8's contiguous share, so neighbouring groups (sharing the item columns' cache
-        // lines) are written through one L2
-        uint64_t blk = blockIdx.x;
-        if (a.xcd) {
-            const uint64_t per = (gridDim.x + 7) / 8;
-            blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-        }
-        g = blk * (blockDim.x >> 6) + wave;
+    // blocks are dealt round-robin to the 8 XCDs: with xcd = 1, block b takes the b/8-th slot
+    // of XCD b%8's contiguous share, so neighbouring groups (sharing the item columns' cache
+    // lines) are written through one L2
+    uint64_t blk = blockIdx.x;
+    if (a.xcd) {
+        const uint64_t per = (gridDim.x + 7) / 8;
+        blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     }
+    const uint64_t g = blk * (blockDim.x >> 6) + wave;
     const uint64_t base = g * 64;
-    __shared__ uint64_t xch[DEC_WAVES + 1]; // ONEPASS: the block's wave totals, then its base
-    if (base >= a.n) {
-        if constexpr (ONEPASS) onepass_base(a, 0u, lane, xch); // the block's barriers
-        return;
-    }
+    if (base >= a.n) return;
     // per wave: the slab, then (RANGES) the item range window
     uint8_t *slab = smem + wave * (a.slab + (RANGES ? NESTED_RANGE_BYTES : 0u));
     __amdgpu_buffer_rsrc_t rsrc =
         uniform_rsrc(a.stream, a.stream_len);
-    if constexpr (!ONEPASS) {
-        // the whole group in the slab; a group whose span exceeds it (a batch whose record sizes
-        // vary a lot) as two halves of 32 records, each staged on its own
-        const uint64_t item_base = uniform64(a.group_base[g]);
-        const Group whole = nested_stage_part(a, rsrc, slab, base, lane, 0, 64);
-        const uint64_t r = base + lane;
-        if (whole.in_lds) {
-            LdsSrc s{(lds_u8 *)slab};
-            nested_group_body<OSpec, ISpec, false, U>(s, whole.rs(), whole.re(),
-                                                   r < a.n, r, g, item_base, lane,
-                                                   whole.to_stream(), a,
-                                                   RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
-            return;
-        }
-        const uint32_t first = nested_decode_part<OSpec, ISpec, RANGES, U>(a, rsrc, slab, g, item_base, lane, 0, 32);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the first half's LDS reads done
-        __builtin_amdgcn_wave_barrier();
-        nested_decode_part<OSpec, ISpec, RANGES, U>(a, rsrc, slab, g, item_base + first, lane, 32, 64);
+    // the whole group in the slab; a group whose span exceeds it (a batch whose record sizes
+    // vary a lot) as two halves of 32 records, each staged on its own
+    const uint64_t item_base = uniform64(a.group_base[g]);
+    const Group whole = nested_stage_part(a, rsrc, slab, base, lane, 0, 64);
+    const uint64_t r = base + lane;
+    if (whole.in_lds) {
+        LdsSrc s{(lds_u8 *)slab};
+        nested_group_body<OSpec, ISpec, U>(s, whole.rs(), whole.re(), r < a.n, r, item_base, lane, whole.to_stream(), a,
+                                           RANGES ? (uint32_t *)(slab + a.slab) : nullptr);
         return;
     }
-    const Group gr = nested_stage(a, rsrc, slab, base, lane);
-    const uint64_t r = base + lane;
-    const bool valid = r < a.n;
-    const uint64_t item_base = 0;
-    if (gr.in_lds) {
-        LdsSrc s{(lds_u8 *)slab};
-        nested_group_body<OSpec, ISpec, ONEPASS>(s, gr.rs(), gr.re(), valid, r, g, item_base, lane,
-                                                 gr.to_stream(), a,
-                                                 RANGES ? (uint32_t *)(slab + a.slab) : nullptr, xch);
-    } else {
-        GlobalSrc s{a.stream, a.stream_len};
-        nested_group_body<OSpec, ISpec, ONEPASS>(s, (long long)gr.rec_lo, (long long)gr.rec_hi, valid, r, g,
-                                                 item_base, lane, 0, a, nullptr, xch);
-    }
+    const uint32_t first = nested_decode_part<OSpec, ISpec, RANGES, U>(a, rsrc, slab, g, item_base, lane, 0, 32);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the first half's LDS reads done
+    __builtin_amdgcn_wave_barrier();
+    nested_decode_part<OSpec, ISpec, RANGES, U>(a, rsrc, slab, g, item_base + first, lane, 32, 64);
 }
 
 // Two-pass decode on a WAVE PAIR (round 5; decode_core.hpp decode_flat_pair is the flat
@@ -536,19 +390,12 @@ __device__ __forceinline__ void nested_decode_body(const NestedArgs &a) {
 // waves decode the group's items, alternating rounds of 64 * U items.  Twice the waves per
 // staged byte: the items' LDS reads are latency-bound.  A group larger
 // than the slab: wave 0 alone, in two halves of 32 records (nested_decode_part).
-// SELF: the other waves open each record's list themselves (rec_open + list_open, the generic
-// path's lookup) instead of waiting for wave 0's posted lists.
-// ONEPASS (round 6): no index kernels.  The group's item total is known once wave 0 has posted
-// the lists; wave 0 then publishes it and finds the group's first item by the decoupled
-// look-back over the earlier groups (lookback: groups in block order, a.group_base = one state
-// word per group, zeroed by the launcher), both waves wait for it at a barrier and decode the
-// items.  The stream is read once (the count pass re-read each record's tail).
-template <class OSpec, class ISpec, int U = NESTED_ITEM_U, int P = 2, bool SELF = false, bool ONEPASS = false>
+template <class OSpec, class ISpec, int U = NESTED_ITEM_U, int P = 2>
 __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint64_t g = blockIdx.x;
-    if (a.xcd && !ONEPASS) {
+    if (a.xcd) {
         const uint64_t per = (gridDim.x + 7) / 8;
         g = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     }
@@ -557,7 +404,7 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     uint8_t *slab = smem;
     uint32_t *xl = (uint32_t *)(smem + a.slab); // [4][64]: count, dsize | big << 31, dstart, tstart
     __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(a.stream, a.stream_len);
-    uint64_t item_base = ONEPASS ? 0 : uniform64(a.group_base[g]);
+    const uint64_t item_base = uniform64(a.group_base[g]);
     DecodeArgs d;
     d.stream = a.stream;
     d.stream_len = a.stream_len;
@@ -570,13 +417,6 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     const Group gr = make_group(d, base, lane, lo, hi, a.slab);
     if (!gr.in_lds) {
         if (wave == 0) {
-            if constexpr (ONEPASS) { // the group's item total from HBM first, then its base
-                GlobalSrc gs{a.stream, a.stream_len};
-                const uint32_t cnt = base + lane < a.n ? record_count(gs, (long long)gr.rec_lo, (long long)gr.rec_hi, a) : 0u;
-                const uint32_t tot = wave_sum(cnt);
-                item_base = uniform64(lookback(a.group_base, g, tot, lane));
-                if (g == (a.n - 1) / 64 && lane == 0) *a.total = item_base + tot;
-            }
             const uint32_t first = nested_decode_part<OSpec, ISpec, false, U>(a, rsrc, slab, g, item_base, lane, 0, 32);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the first half's LDS reads done
             __builtin_amdgcn_wave_barrier();
@@ -592,20 +432,15 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     const bool valid = r < a.n;
     ListInfo li = {0, 0, 0, 0, false};
     const int rs = gr.rs(), re = gr.re();
-    if constexpr (SELF) {
-        if (valid) {
-            if (wave == 0) li = decode_outer<OSpec>(s, rs, re, r, to_stream, a);
-            else li = list_open(s, rec_open(s, rs, re), a);
-        }
-    } else if (wave == 0) {
+    if (wave == 0) {
         if (valid) li = decode_outer<OSpec>(s, rs, re, r, to_stream, a);
         xl[lane] = li.count;
         xl[64 + lane] = li.dsize | ((uint32_t)li.big << 31);
         xl[128 + lane] = (uint32_t)li.dstart;
         xl[192 + lane] = (uint32_t)li.tstart;
     }
-    if constexpr (!SELF) __syncthreads(); // the lists are posted
-    if (!SELF && wave != 0) {
+    __syncthreads(); // the lists are posted
+    if (wave != 0) {
         li.count = xl[lane];
         const uint32_t ds = xl[64 + lane];
         li.dsize = ds & 0x7fffffffu;
@@ -616,18 +451,6 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     const uint32_t incl = wave_incl_scan(li.count, lane);
     const uint32_t excl = incl - li.count;
     const uint32_t total = __shfl(incl, 63);
-    if constexpr (ONEPASS) {
-        uint64_t *xb = (uint64_t *)(xl + 256); // the group's base, from wave 0 to the others
-        if (wave == 0) {
-            const uint64_t b = uniform64(lookback(a.group_base, g, total, lane));
-            if (lane == 0) {
-                *xb = b;
-                if (g == (a.n - 1) / 64) *a.total = b + total;
-            }
-        }
-        __syncthreads(); // the base is posted
-        item_base = uniform64(*xb);
-    }
     if (wave == 0 && valid) {
         a.item_begin[r] = (uint32_t)(item_base + excl);
         if (r == a.n - 1) a.item_begin[a.n] = (uint32_t)(item_base + incl);

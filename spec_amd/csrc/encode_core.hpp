@@ -951,21 +951,8 @@ struct SpecEnc {
         em.template put_heap_short<RUN_M>(w, 0u, (uint32_t)TB + L + 2);
     }
 
-    // ---- the write pass on a wave pair (encode_write_pair_body): wave 0 emits fields [0, H),
-    // wave 1 fields [H, N), the table and the trailer ----
-    // x.end[F..E) = base + the field sizes through each field: the ends the emitter records,
-    // known from the sizes before any byte is written
-    template <int F, int E>
-    static __device__ __forceinline__ uint32_t range_ends(const EncFields &f, Rec &x, uint64_t r, uint32_t base) {
-        if constexpr (F < E) {
-            bool err = false;
-            const uint32_t s = (uint32_t)data_size<F, NoLists, F + 1>(f, x, r, false, err, NoLists());
-            x.end[F] = base + s;
-            return range_ends<F + 1, E>(f, x, r, base + s);
-        } else {
-            return base;
-        }
-    }
+    // ---- hooks of the nested write pass on wave pairs (encode_nested_core.hpp
+    // nested_enc_write_pair_body): each wave emits a range of the outer fields ----
     // the values of fields [F0, F1) from em.pos (no finish: the pending dword stays in em.acc)
     template <int F0, int F1, class E, class Lists = NoListEmit>
     static __device__ __forceinline__ void emit_range(const EncFields &f, E &em, Rec &x, decltype(em.pos) start,
@@ -1151,30 +1138,6 @@ __device__ __forceinline__ void encode_write_body(const A &a, uint8_t *smem) {
 
 constexpr size_t enc_write_lds_bytes() { return ENC_LDS_HEAD + (size_t)(ENC_BLOCK / 64) * ENC_SLAB; }
 
-// ---- the write pass on wave PAIRS (schema-specialised encoders) ---------------------------
-// A 512-thread block takes the size pass's 256-record block as four groups of 64 records; each
-// group is written by a wave PAIR sharing one LDS slab: wave 0 emits fields [0, H) of the 64
-// records, wave 1 fields [H, N) from each record's position of field H, then the table and the
-// trailer (the ends of fields [0, H) come from wave 0 through LDS, known from the sizes before
-// any byte is written).  Twice the waves per slab: one wave's LDS stores and heap loads overlap
-// the other's emission (the decoder's wave pairs, decode_flat_pair, are the same lever).
-// Ordering: a HEAD_ST4 emitter's first dword store covers <= 3 bytes below its start (the bytes
-// of the previous lane's record, or of wave 0's half of the same record), and every emitter
-// keeps its last partial dword pending; all whole-dword stores of both waves happen before a
-// block barrier and every pending tail is stored bytewise after it, so each byte's last writer
-// is its owner.
-// LDS: wsum[4] | per group: d0 (u32 x 64) | wave 0's field ends (u16 x H x 64) | slab.
-constexpr int ENC_PAIR_BLOCK = 512;
-constexpr int ENC_PAIR_HEAD = 64;
-__host__ __device__ constexpr uint32_t enc_pair_xch_bytes(int h) { return (uint32_t)(256 + 128 * h + 15) & ~15u; }
-// the slab of one group: four groups' slabs and exchanges in <= 80 KiB (two blocks per CU)
-__host__ __device__ constexpr uint32_t enc_pair_slab_bytes(int h) {
-    return ((81920u - ENC_PAIR_HEAD) / 4 - enc_pair_xch_bytes(h)) & ~15u;
-}
-__host__ __device__ constexpr uint32_t enc_pair_lds_bytes(int h) {
-    return ENC_PAIR_HEAD + 4 * (enc_pair_xch_bytes(h) + enc_pair_slab_bytes(h));
-}
-
 // copy_slab_out by T threads (one 16-byte store per thread and chunk)
 template <int T>
 __device__ __forceinline__ void copy_slab_out_t(const uint8_t *slab, uint8_t *gbase, uint64_t head, uint64_t lim,
@@ -1201,104 +1164,6 @@ __device__ __forceinline__ void copy_slab_out_t(const uint8_t *slab, uint8_t *gb
     const uint64_t tb = (l16 << 4) > hend ? (l16 << 4) : hend;
     if (tid < 16 && head + tid < hend) gbase[head + tid] = sb[head + tid];
     if (tid >= 16 && tid < 32 && tb + (tid - 16) < lim) gbase[tb + (tid - 16)] = sb[tb + (tid - 16)];
-}
-
-template <class P, int H>
-__device__ __forceinline__ void encode_write_pair_body(const EncodeArgs &a, uint8_t *smem) {
-    static_assert(H >= 1 && H < P::N, "the split leaves fields on both waves");
-    constexpr uint32_t XB = enc_pair_xch_bytes(H), SB = enc_pair_slab_bytes(H);
-    uint64_t *wsum = (uint64_t *)smem;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, grp = wave >> 1, half = wave & 1;
-    uint8_t *gx = smem + ENC_PAIR_HEAD + grp * (XB + SB);
-    uint32_t *xd0 = (uint32_t *)gx;                   // wave 0's data bytes per record
-    uint16_t *xend = (uint16_t *)(gx + 256);          // wave 0's field ends [field][lane]
-    uint8_t *slab = gx + XB;
-    const uint64_t r = (uint64_t)blockIdx.x * ENC_BLOCK + grp * 64 + lane;
-    const bool valid = r < a.n;
-    const uint64_t rr = valid ? r : a.n - 1;
-    typename P::Rec x;
-    if (half == 0) {
-        P::template load_col<0, H>(a.f, rr, x);
-        P::template load_heap<0, H>(a.f, x);
-    } else {
-        P::template load_col<H, P::N>(a.f, rr, x);
-        P::template load_heap<H, P::N>(a.f, x);
-    }
-    const uint64_t total = a.block_sums[a.nblocks], blk_pre = a.block_sums[blockIdx.x];
-    if (total > a.out_cap) return; // capacity error or encoder error (total == ~0): block-uniform
-    bool err = false;
-    uint32_t dmine;
-    if (half == 0) {
-        dmine = P::template range_ends<0, H>(a.f, x, rr, 0u);
-        xd0[lane] = dmine;
-#pragma unroll
-        for (int f = 0; f < H; f++) xend[f * 64 + lane] = (uint16_t)x.end[f];
-    } else {
-        dmine = (uint32_t)P::template data_size<H, NoLists, P::N>(a.f, x, rr, false, err, NoLists());
-    }
-    __syncthreads(); // (1) wave 0's sizes and ends are in LDS
-    const uint32_t d0 = half == 0 ? dmine : xd0[lane];
-    const uint64_t data = (uint64_t)d0 + (half == 0 ? 0u : dmine);
-    uint64_t tot = 0, data_all = data;
-    RecSize rs;
-    if (half == 1) {
-        rs.data = data_all;
-        rs.big = P::kBigForced | (data_all > 65535);
-        const uint64_t tsize = (uint64_t)P::N * (rs.big ? 6 : 3);
-        rs.total = data_all + tsize + vlen32((uint32_t)data_all) + vlen32((uint32_t)tsize) + 1;
-        tot = valid ? rs.total : 0;
-    }
-    // wave 1 owns the record sizes: its scan gives the group's offsets; wave 0 reads its starts
-    uint64_t xs = tot;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = __shfl_up(xs, o);
-        if (lane >= o) xs += y;
-    }
-    uint64_t *xstart = (uint64_t *)slab; // (the slab is free until the emission starts)
-    if (half == 1) {
-        if (lane == 63) wsum[grp] = xs;
-        xstart[lane] = xs - tot; // group-relative start of the record
-    }
-    __syncthreads(); // (2) group sums and starts
-    uint64_t pre = blk_pre;
-    for (int g = 0; g < grp; g++) pre += wsum[g];
-    const uint64_t start = pre + xstart[lane];
-    const uint64_t gtot = wsum[grp];
-    if (half == 1 && valid) a.ends[r] = a.ends_base + start + rs.total;
-    const uint64_t gbase_r = (uint64_t)blockIdx.x * ENC_BLOCK + grp * 64;
-    const bool live = gbase_r < a.n; // group-uniform
-    const uint64_t S = pre, E = pre + gtot;
-    const uint64_t head = ((uint64_t)(a.out + S)) & 15;
-    const bool fits = live && head + (E - S) + 16 <= (uint64_t)SB;
-    __syncthreads(); // (3) xstart read: the slab may be written
-    if (!live) return;
-    if (!fits) {
-        // a group larger than its slab: wave 0 writes each record straight to HBM (every field)
-        if (half == 0 && valid) {
-            const typename P::Rec all = P::load(a.f, r);
-            RecSize rs0 = P::size(a.f, all, r, false, err);
-            GlobalSink k{a.out};
-            P::emit(a.f, k, (long long)start, r, all, rs0, (const uint8_t *)nullptr);
-        }
-        return;
-    }
-    LdsSink k{slab, (int)(smem + ENC_PAIR_HEAD - 4 - slab)}; // dummy: the last header dword
-    const int p0 = (int)(head + (start - S));
-    Emit<LdsSink, int, true> em(k, half == 0 ? p0 : p0 + (int)d0);
-    if (valid) {
-        if (half == 0) {
-            P::template emit_range<0, H>(a.f, em, x, p0, r);
-        } else {
-#pragma unroll
-            for (int f = 0; f < H; f++) x.end[f] = xend[f * 64 + lane];
-            P::template emit_range<H, P::N>(a.f, em, x, p0, r);
-            P::emit_table_trailer(em, x, rs);
-        }
-    }
-    __syncthreads(); // (4) every whole-dword store of the group is done
-    if (valid) em.finish(); // the pending tails, bytewise: the owners write last
-    __syncthreads(); // (5) the slab is complete
-    copy_slab_out_t<128>(slab, a.out + S - head, head, head + (E - S), threadIdx.x & 127);
 }
 
 } // namespace spec

@@ -510,7 +510,7 @@ __device__ __forceinline__ void emit_item_range(const NestedEncodeArgs &a, const
 // written by a wave PAIR sharing the group's prefix and slab (the same LDS per group as the
 // one-wave pass, twice the waves per CU).  Wave 0 emits the records' outer fields before the
 // list field (A1) and the items of records [0, R0); wave 1 the items of records [R0, 64)
-// concurrently (R0: the record boundary near SPEC_AB_NENC_SPLIT % of the group's items); after a
+// concurrently (R0: the record boundary near NENC_SPLIT % of the group's items); after a
 // barrier wave 0 emits the rest of each record (A2: list table and trailer, later fields, outer
 // table and trailer) with an emitter that never stores below its start, and both copy the slab
 // out.  Ordering: the HEAD_ST4 emitters of A1 and of the items store whole dwords, the first
@@ -521,13 +521,7 @@ __device__ __forceinline__ void emit_item_range(const NestedEncodeArgs &a, const
 // HEAD = 4 (spec_encode_nested_frames, as nested_enc_write_body): the frame head is A1's first
 // append, in front of the fields before the list — with the list as the first field it is all of
 // A1, and the <= 3 of its bytes an item's first dword store may cover are A1's pending tail.
-#ifndef SPEC_AB_NENC_SPLIT
-#define SPEC_AB_NENC_SPLIT 45
-#endif
-// measurement builds only (wrong bytes): skip the items (1), the copy-out (2), the outer records (4)
-#ifndef SPEC_AB_NENC_SKIP
-#define SPEC_AB_NENC_SKIP 0
-#endif
+constexpr int NENC_SPLIT = 45; // wave 0's share of a group's items, in percent (it also emits A1 and A2)
 template <class OP, class IP, int HEAD = 0>
 __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArgs &a, uint8_t *smem) {
     constexpr int LF = OP::list_field();
@@ -602,10 +596,10 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
             for (uint32_t q = k0; q < k1; q++) pre[q] = (uint32_t)((int)pre[q] + delta);
         }
     }
-    // the split: the first record whose items start at or past SPEC_AB_NENC_SPLIT % of the group's
+    // the split: the first record whose items start at or past NENC_SPLIT % of the group's
     uint32_t K0 = cnt;
     if (staged) {
-        const uint64_t m = __ballot(valid && (uint64_t)(b - I0) * 100 >= (uint64_t)cnt * SPEC_AB_NENC_SPLIT);
+        const uint64_t m = __ballot(valid && (uint64_t)(b - I0) * 100 >= (uint64_t)cnt * NENC_SPLIT);
         if (m) K0 = __builtin_amdgcn_readlane(b, __builtin_ctzll(m)) - I0;
     }
     __syncthreads(); // (3) item positions
@@ -614,12 +608,12 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
     Emit<LdsSink, int, true> em(k, p0);
     if (staged) {
         if (half == 0) {
-            if (valid && !(SPEC_AB_NENC_SKIP & 4)) { // A1, its tail left pending
+            if (valid) { // A1, its tail left pending
                 if constexpr (HEAD != 0) em.put4(bswap32((uint32_t)rs.total));
                 OP::template emit_range<0, LF>(a.outer, em, xo, m0, r);
             }
-            if (!(SPEC_AB_NENC_SKIP & 1)) emit_item_range<IP>(a, k, pre, I0, 0u, K0, inv_item, lane);
-        } else if (!(SPEC_AB_NENC_SKIP & 1)) {
+            emit_item_range<IP>(a, k, pre, I0, 0u, K0, inv_item, lane);
+        } else {
             emit_item_range<IP>(a, k, pre, I0, K0, cnt, inv_item, lane);
         }
     } else if (half == 0 && valid) {
@@ -631,7 +625,7 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
         emit_message(a.outer, g, (long long)start + HEAD, r, rs, inv_outer, le);
     }
     __syncthreads(); // (4) every whole-dword store of A1 and of the items is done
-    if (staged && half == 0 && valid && !(SPEC_AB_NENC_SKIP & 4)) {
+    if (staged && half == 0 && valid) {
         // A2: the same emitter from the list field on; the hook stores A1's pending tail bytewise
         // and resumes past the items with their last bytes read back (WaveListEmit merge_slab)
         WaveListEmit le{pre + (b - I0), ls.count, (uint32_t)ls.data, ls.big, 0, slab};
@@ -640,7 +634,7 @@ __device__ __forceinline__ void nested_enc_write_pair_body(const NestedEncodeArg
         em.finish();
     }
     __syncthreads(); // (5) the group's slab is complete
-    if (staged && !(SPEC_AB_NENC_SKIP & 2)) copy_slab_out_t<128>(slab, a.out + S - head, head, head + (E - S), threadIdx.x & 127);
+    if (staged) copy_slab_out_t<128>(slab, a.out + S - head, head, head + (E - S), threadIdx.x & 127);
 }
 
 } // namespace spec

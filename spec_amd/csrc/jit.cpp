@@ -36,16 +36,23 @@
 #include <cstring>
 
 #include "spec_internal.hpp"
-#include "tree_core.hpp"
+#include "tree_internal.hpp"
 
 namespace {
 
 // the device sources, embedded at build time (Makefile -> build/rtc_sources.inc)
 #include "build/rtc_sources.inc"
 
+// The kernels of a generated module, by program (load() has their names)
+enum DecodeFn { DEC_PAIR, DEC_PAIR_ERR }; // the errmask variant: spec_decode_flat_errors
+enum EncodeFn { ENC_SIZE, ENC_WRITE, ENC_WRITE_FRAMES };
+enum NestedFn { NEST_PAIR, NEST_RANGES };
+enum NestedEncFn { NENC_SIZE, NENC_WRITE, NENC_WRITE_FRAMES, NENC_WRITE_PAIR, NENC_WRITE_PAIR_FRAMES };
+constexpr int MAX_FN = 5;
+
 struct Entry {
     hipModule_t mod = nullptr;
-    hipFunction_t fn[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipFunction_t fn[MAX_FN] = {};
     bool failed = false;
 };
 
@@ -122,7 +129,7 @@ enum Prog { DECODE = 0, ENCODE = 1, NESTED = 2, NESTED_ENC = 3, TREE = 4 };
 
 std::string key_of(const spec_schema *s, int device, Prog p) {
     std::ostringstream k;
-    k << (p == ENCODE || p == NESTED_ENC ? "enc:" : "dec:") << device << ':' << (spec::persistent_decode() ? 'p' : 'o') << ':';
+    k << (p == ENCODE || p == NESTED_ENC ? "enc:" : "dec:") << device << ':';
     for (uint32_t f = 0; f < s->nfields; f++) k << s->fields[f].tag << '/' << (int)s->fields[f].kind << ',';
     return k.str();
 }
@@ -148,27 +155,19 @@ void emit_spec(std::ostringstream &o, const char *name, const spec_schema *s) {
     o << "};\n  static constexpr bool big = " << (big ? "true" : "false") << ";\n};\n";
 }
 
-// waves per 64-record group of the flat decode (decode_core.hpp decode_flat_pair); build-time A/B
-#ifndef SPEC_AB_FLAT_WAVES
-#define SPEC_AB_FLAT_WAVES 2
-#endif
+// waves per 64-record group of the flat decode (decode_core.hpp decode_flat_pair)
+constexpr int FLAT_WAVES = 2;
 
 std::string generate_decode(const spec_schema *s) {
     std::ostringstream o;
     o << "#include \"decode_core.hpp\"\n";
     emit_spec(o, "GenSpec", s);
-    const char *pers = spec::persistent_decode() ? "true" : "false";
     // schemas on decode_core.hpp fast_wide get kernels of their own names (traces tell them apart)
     bool big = false;
     for (uint32_t f = 0; f < s->nfields; f++) big = big || s->fields[f].tag > 255;
     const char *w = (s->nfields > (uint32_t)spec::FAST_MAX_FIELDS || big) ? "_wide" : "";
-    o << "extern \"C\" __global__ __launch_bounds__(256) void spec_decode_flat" << w << "_jit(spec::DecodeArgs a) {\n"
-      << "  spec::decode_flat_entry<" << pers << ", GenSpec>(a);\n}\n"
-      << "extern \"C\" __global__ __launch_bounds__(256) void spec_decode_flat" << w << "_err_jit(spec::DecodeArgs a) {\n"
-      << "  spec::decode_flat_entry<" << pers << ", GenSpec, true>(a);\n}\n";
-    // the wave-pair kernel (decode_core.hpp decode_flat_pair), the default launch for every
-    // schema (decode_flat.hip SPEC_AB_FLAT_PAIR)
-    const int P = SPEC_AB_FLAT_WAVES;
+    // the wave-pair kernel (decode_core.hpp decode_flat_pair): every schema's launch
+    const int P = FLAT_WAVES;
     o << "extern \"C\" __global__ __launch_bounds__(" << 64 * P << ") void spec_decode_flat" << w
       << "_pair_jit(spec::DecodeArgs a) {\n"
       << "  spec::decode_flat_pair<GenSpec, false, " << P << ">(a);\n}\n"
@@ -179,18 +178,10 @@ std::string generate_decode(const spec_schema *s) {
 }
 
 // The nested decode's wave group (decode_nested_core.hpp nested_decode_pair): waves per group
-// and item rounds of 64 per wave in flight; build-time A/B only.
-#ifndef SPEC_AB_NESTED_WAVES
-#define SPEC_AB_NESTED_WAVES 2
-#endif
-#ifndef SPEC_AB_NESTED_U
-#define SPEC_AB_NESTED_U 1
-#endif
-#ifndef SPEC_AB_NESTED_SELF
-#define SPEC_AB_NESTED_SELF 0
-#endif
+// and item rounds of 64 per wave in flight.
+constexpr int NESTED_WAVES = 2, NESTED_U = 1;
 
-// One-pass nested decode: outer and item fast paths where the schema has one.
+// Nested decode after the index kernels: outer and item fast paths where the schema has one.
 std::string generate_nested(const spec_nested_schema *s) {
     std::ostringstream o;
     o << "#include \"decode_nested_core.hpp\"\n";
@@ -199,20 +190,11 @@ std::string generate_nested(const spec_nested_schema *s) {
     if (fi) emit_spec(o, "GenItem", &s->item);
     const std::string specs = std::string(fo ? "GenOuter" : "spec::RuntimeSpec") + ", " +
                               (fi ? "GenItem" : "spec::RuntimeSpec");
-    o << "extern \"C\" __global__ __launch_bounds__(256) void spec_decode_nested_jit(spec::NestedArgs a) {\n"
+    o << "extern \"C\" __global__ __launch_bounds__(64) void spec_decode_nested3_jit(spec::NestedArgs a) {\n"
       << "  spec::nested_decode_body<" << specs << ", true>(a);\n}\n"
-      << "extern \"C\" __global__ __launch_bounds__(64) void spec_decode_nested2_jit(spec::NestedArgs a) {\n"
-      << "  spec::nested_decode_body<" << specs << ", false>(a);\n}\n"
-      << "extern \"C\" __global__ __launch_bounds__(64) void spec_decode_nested3_jit(spec::NestedArgs a) {\n"
-      << "  spec::nested_decode_body<" << specs << ", false, true>(a);\n}\n"
-      << "extern \"C\" __global__ __launch_bounds__(" << 64 * SPEC_AB_NESTED_WAVES
+      << "extern \"C\" __global__ __launch_bounds__(" << 64 * NESTED_WAVES
       << ") void spec_decode_nested_pair_jit(spec::NestedArgs a) {\n"
-      << "  spec::nested_decode_pair<" << specs << ", " << SPEC_AB_NESTED_U << ", " << SPEC_AB_NESTED_WAVES
-      << ", " << (SPEC_AB_NESTED_SELF ? "true" : "false") << ">(a);\n}\n"
-      << "extern \"C\" __global__ __launch_bounds__(" << 64 * SPEC_AB_NESTED_WAVES
-      << ") void spec_decode_nested_pairlb_jit(spec::NestedArgs a) {\n"
-      << "  spec::nested_decode_pair<" << specs << ", " << SPEC_AB_NESTED_U << ", " << SPEC_AB_NESTED_WAVES
-      << ", false, true>(a);\n}\n";
+      << "  spec::nested_decode_pair<" << specs << ", " << NESTED_U << ", " << NESTED_WAVES << ">(a);\n}\n";
     return o.str();
 }
 
@@ -244,18 +226,8 @@ bool has_nested_encoder(const spec_nested_schema *s) {
     return !nested_wide(s) && (has_outer_encoder(&s->outer) || has_encoder(&s->item));
 }
 
-// build-time A/B of the nested pair write pass (encode_nested_core.hpp), passed into the
-// generated source: the JIT compile sees only what the source defines
-#ifndef SPEC_AB_NENC_SPLIT
-#define SPEC_AB_NENC_SPLIT 45
-#endif
-#ifndef SPEC_AB_NENC_SKIP
-#define SPEC_AB_NENC_SKIP 0
-#endif
 std::string generate_nested_encode(const spec_nested_schema *s) {
     std::ostringstream o;
-    if (SPEC_AB_NENC_SPLIT != 45) o << "#define SPEC_AB_NENC_SPLIT " << SPEC_AB_NENC_SPLIT << "\n";
-    if (SPEC_AB_NENC_SKIP) o << "#define SPEC_AB_NENC_SKIP " << SPEC_AB_NENC_SKIP << "\n";
     o << "#include \"encode_nested_core.hpp\"\n";
     const bool fo = has_outer_encoder(&s->outer), fi = has_encoder(&s->item);
     if (fo) emit_enc_spec(o, "GenOuter", &s->outer);
@@ -283,47 +255,6 @@ std::string generate_nested_encode(const spec_nested_schema *s) {
     return o.str();
 }
 
-// The write pass on wave pairs (encode_core.hpp encode_write_pair_body): wave 0 takes fields
-// [0, H), wave 1 fields [H, N) plus the table and trailer.  H balances a per-kind emission cost
-// (instructions of the HEAD_ST4 emitter: a string's heap copy and funnel shifts dominate, the
-// table + trailer costs about two strings' worth for 16 fields); 0 = no pair kernel (one field).
-// Build-time A/B (round 6): bit-exact (204 flat/wide/golden/C-ABI GPU tests), but Flat16 encode
-// 0.1255-0.1293 ms with pairs vs 0.1249-0.1287 without (gpurun_out/encab1, three alternating runs
-// on one box): a one-wave group already has all 64 records' loads in flight, so a second wave per
-// slab adds issue slots, not memory parallelism.  Off by default.
-#ifndef SPEC_AB_ENC_PAIR
-#define SPEC_AB_ENC_PAIR 0
-#endif
-int enc_pair_split(const spec_schema *s) {
-    const int n = (int)s->nfields;
-    if (!SPEC_AB_ENC_PAIR || n < 2) return 0;
-    auto cost = [](int k) {
-        switch (k) {
-        case SPEC_KIND_BOOL: case SPEC_KIND_BYTE: return 8;
-        case SPEC_KIND_FLOAT32: return 10;
-        case SPEC_KIND_INT64: case SPEC_KIND_UINT64: return 14;
-        case SPEC_KIND_BIN128: return 16;
-        case SPEC_KIND_BIN256: return 28;
-        case SPEC_KIND_STRING: case SPEC_KIND_BYTES: return 100;
-        }
-        return 12; // 16/32-bit ints, float64, bin64
-    };
-    int total = 40 + 5 * n, pre[SPEC_KFIELDS + 1] = {0};
-    for (int f = 0; f < n; f++) {
-        pre[f + 1] = pre[f] + cost(s->fields[f].kind);
-        total += cost(s->fields[f].kind);
-    }
-    int best = 1, best_max = 1 << 30;
-    for (int h = 1; h < n; h++) {
-        const int m = std::max(pre[h], total - pre[h]);
-        if (m < best_max) {
-            best_max = m;
-            best = h;
-        }
-    }
-    return best;
-}
-
 std::string generate_encode(const spec_schema *s) {
     std::ostringstream o;
     o << "#include \"encode_core.hpp\"\n";
@@ -339,10 +270,6 @@ std::string generate_encode(const spec_schema *s) {
       << "extern \"C\" __global__ __launch_bounds__(256) void spec_encode_write_frames_jit(spec::EncodeArgs a) {\n"
       << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
       << "  spec::encode_write_body<P, spec::EncodeArgs, 4>(a, smem);\n}\n";
-    if (const int h = enc_pair_split(s))
-        o << "extern \"C\" __global__ __launch_bounds__(512) void spec_encode_write_pair_jit(spec::EncodeArgs a) {\n"
-          << "  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];\n"
-          << "  spec::encode_write_pair_body<P, " << h << ">(a, smem);\n}\n";
     return o.str();
 }
 
@@ -354,25 +281,30 @@ const char *prog_name(Prog p) {
                              : "spec_decode_flat_jit.hip";
 }
 
+// SPEC_AMD_JIT_DUMP=prefix: the generated source is written to <prefix><program>.hip before the
+// compile (a slow compile can be inspected while it runs), the code object to <prefix><program>.co
+// after it (ISA inspection)
+void dump(Prog p, const char *ext, const char *data, size_t n) {
+    const char *d = getenv("SPEC_AMD_JIT_DUMP");
+    if (!d) return;
+    const std::string path = std::string(d) + (p == ENCODE       ? "encode"
+                                               : p == TREE       ? "tree"
+                                               : p == NESTED     ? "nested"
+                                               : p == NESTED_ENC ? "nested_encode"
+                                                                 : "decode") + ext;
+    if (FILE *f = fopen(path.c_str(), "wb")) {
+        fwrite(data, 1, n, f);
+        fclose(f);
+    }
+}
+
 // hiprtc compile only; returns the code object (empty on failure)
 std::vector<char> compile_uncached(const std::string &src, Prog p, const char *const *opts_in, int nopts) {
     const char *hdr_src[7] = {kSpecDeviceHpp, kDecodeCoreHpp, kEncodeCoreHpp, kDecodeNestedCoreHpp,
                               kEncodeNestedCoreHpp, kTreeCoreHpp, kTreeDecodeCoreHpp};
     const char *hdr_name[7] = {"spec_device.hpp", "decode_core.hpp", "encode_core.hpp", "decode_nested_core.hpp",
                                "encode_nested_core.hpp", "tree_core.hpp", "tree_decode_core.hpp"};
-    // SPEC_AMD_JIT_DUMP=prefix: the source is written before the compile (a slow compile can be
-    // inspected while it runs), the code object after it
-    if (const char *d = getenv("SPEC_AMD_JIT_DUMP")) {
-        const std::string base = std::string(d) + (p == ENCODE       ? "encode"
-                                                   : p == TREE       ? "tree"
-                                                   : p == NESTED     ? "nested"
-                                                   : p == NESTED_ENC ? "nested_encode"
-                                                                     : "decode");
-        if (FILE *f = fopen((base + ".hip").c_str(), "w")) {
-            fwrite(src.data(), 1, src.size(), f);
-            fclose(f);
-        }
-    }
+    dump(p, ".hip", src.data(), src.size());
     hiprtcProgram prog;
     if (hiprtcCreateProgram(&prog, src.c_str(), prog_name(p), 7, hdr_src, hdr_name) != HIPRTC_SUCCESS) return {};
     // the product kernels are compiled with fixed options only: no environment variable can
@@ -398,17 +330,7 @@ std::vector<char> compile_uncached(const std::string &src, Prog p, const char *c
     std::vector<char> code(cs);
     hiprtcGetCode(prog, code.data());
     hiprtcDestroyProgram(&prog);
-    if (const char *d = getenv("SPEC_AMD_JIT_DUMP")) { // the code object (ISA inspection)
-        std::string base = std::string(d) + (p == ENCODE       ? "encode"
-                                             : p == TREE       ? "tree"
-                                             : p == NESTED     ? "nested"
-                                             : p == NESTED_ENC ? "nested_encode"
-                                                               : "decode");
-        if (FILE *f = fopen((base + ".co").c_str(), "wb")) {
-            fwrite(code.data(), 1, code.size(), f);
-            fclose(f);
-        }
-    }
+    dump(p, ".co", code.data(), code.size());
     return code;
 }
 
@@ -491,48 +413,58 @@ std::vector<char> compile_code(const spec_schema *s, Prog p) {
     return compile_source(p == ENCODE ? generate_encode(s) : generate_decode(s), p);
 }
 
+// A kernel of a generated module: its slot in Entry::fn and its name.  Optional kernels are
+// generated together or not at all.
+struct Kernel {
+    int fn;
+    const char *name;
+    bool optional = false;
+};
+
+bool get_kernels(Entry &e, std::initializer_list<Kernel> kernels) {
+    bool some = false, all = true;
+    for (const Kernel &k : kernels) {
+        const bool got = hipModuleGetFunction(&e.fn[k.fn], e.mod, k.name) == hipSuccess;
+        if (!got) {
+            (void)hipGetLastError();
+            e.fn[k.fn] = nullptr;
+            if (!k.optional) return false;
+        }
+        if (k.optional) {
+            some = some || got;
+            all = all && got;
+        }
+    }
+    return all || !some;
+}
+
+// The required and optional kernels of each program's module
+bool load_kernels(Entry &e, Prog p) {
+    switch (p) {
+    case DECODE: // (a wide / big-table schema's kernels have names of their own: generate_decode)
+        return get_kernels(e, {{DEC_PAIR, "spec_decode_flat_pair_jit"}, {DEC_PAIR_ERR, "spec_decode_flat_err_pair_jit"}}) ||
+               get_kernels(e, {{DEC_PAIR, "spec_decode_flat_wide_pair_jit"},
+                               {DEC_PAIR_ERR, "spec_decode_flat_wide_err_pair_jit"}});
+    case ENCODE:
+        return get_kernels(e, {{ENC_SIZE, "spec_encode_size_jit"},
+                               {ENC_WRITE, "spec_encode_write_jit"},
+                               {ENC_WRITE_FRAMES, "spec_encode_write_frames_jit"}});
+    case NESTED:
+        return get_kernels(e, {{NEST_PAIR, "spec_decode_nested_pair_jit"}, {NEST_RANGES, "spec_decode_nested3_jit"}});
+    case NESTED_ENC: // (the pair kernels: only with a specialised outer encoder)
+        return get_kernels(e, {{NENC_SIZE, "spec_encode_nested_size_jit"},
+                               {NENC_WRITE, "spec_encode_nested_write_jit"},
+                               {NENC_WRITE_FRAMES, "spec_encode_nested_write_frames_jit"},
+                               {NENC_WRITE_PAIR, "spec_encode_nested_write_pair_jit", true},
+                               {NENC_WRITE_PAIR_FRAMES, "spec_encode_nested_write_pair_frames_jit", true}});
+    case TREE: break; // (jit_tree_kernels loads a tree's module)
+    }
+    return false;
+}
+
 Entry load(const std::vector<char> &code, Prog p) {
     Entry e;
-    if (code.empty()) {
-        e.failed = true;
-        return e;
-    }
-    const char *names[4][4] = {{"spec_decode_flat_jit", "spec_decode_flat_err_jit", "spec_decode_flat_pair_jit",
-                                "spec_decode_flat_err_pair_jit"},
-                               {"spec_encode_size_jit", "spec_encode_write_jit", nullptr, // ([2]: the pair kernel, optional)
-                                "spec_encode_write_frames_jit"},
-                               {"spec_decode_nested_jit", "spec_decode_nested2_jit", "spec_decode_nested3_jit",
-                                "spec_decode_nested_pair_jit"},
-                               {"spec_encode_nested_size_jit", "spec_encode_nested_write_jit", nullptr, // ([2], [4]: the pair kernels)
-                                "spec_encode_nested_write_frames_jit"}};
-    bool ok = hipModuleLoadData(&e.mod, code.data()) == hipSuccess;
-    if (ok && p == DECODE && hipModuleGetFunction(&e.fn[0], e.mod, names[p][0]) != hipSuccess) {
-        (void)hipGetLastError(); // a wide / big-table schema (generate_decode): its own kernel names
-        names[p][0] = "spec_decode_flat_wide_jit";
-        names[p][1] = "spec_decode_flat_wide_err_jit";
-        names[p][2] = "spec_decode_flat_wide_pair_jit";
-        names[p][3] = "spec_decode_flat_wide_err_pair_jit";
-    }
-    for (int i = 0; ok && i < 4; i++)
-        if (names[p][i]) ok = hipModuleGetFunction(&e.fn[i], e.mod, names[p][i]) == hipSuccess;
-    if (ok && p == ENCODE && hipModuleGetFunction(&e.fn[2], e.mod, "spec_encode_write_pair_jit") != hipSuccess) {
-        (void)hipGetLastError(); // a one-field schema has no pair kernel
-        e.fn[2] = nullptr;
-    }
-    if (ok && p == NESTED && hipModuleGetFunction(&e.fn[4], e.mod, "spec_decode_nested_pairlb_jit") != hipSuccess) {
-        (void)hipGetLastError();
-        e.fn[4] = nullptr;
-    }
-    if (ok && p == NESTED_ENC &&
-        hipModuleGetFunction(&e.fn[2], e.mod, "spec_encode_nested_write_pair_jit") != hipSuccess) {
-        (void)hipGetLastError(); // no specialised outer encoder: no pair kernel
-        e.fn[2] = nullptr;
-    }
-    if (ok && p == NESTED_ENC && e.fn[2] &&
-        hipModuleGetFunction(&e.fn[4], e.mod, "spec_encode_nested_write_pair_frames_jit") != hipSuccess) {
-        (void)hipGetLastError();
-        ok = false; // the pair kernels are generated together
-    }
+    const bool ok = !code.empty() && hipModuleLoadData(&e.mod, code.data()) == hipSuccess && load_kernels(e, p);
     if (!ok) {
         (void)hipGetLastError();
         e.failed = true;
@@ -877,47 +809,27 @@ void gen_table_trailer(std::ostringstream &o, const TreeDesc &D, const TTable &T
 // list elements are children written by their tables' later launches into the gaps skipped here.
 // the column reads of direct field k of table T issued before the first byte (values; a
 // sub-message's or list's presence; a sub-message's size)
-// (sfx / rv: the variables' suffix and the row expression, for a writer over two rows at once)
-void gen_field_loads(std::ostringstream &o, const TreeDesc &D, const TTable &T, uint32_t k, bool eager, const char *ind,
-                     const std::string &sfx = "", const std::string &rv = "row") {
+void gen_field_loads(std::ostringstream &o, const TreeDesc &D, const TTable &T, uint32_t k, bool eager, const char *ind) {
     const TField &F = D.f[D.direct[T.d0 + k]];
     if ((F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) || F.kind == spec::K_ANY) {
         if (eager)
-            o << ind << "uint64_t a" << k << sfx << "[4];\n" << ind << "load_value_k<" << (int)F.kind << ">(" << col_expr(F.col)
-              << ", " << rv << ", a" << k << sfx << ");\n";
+            o << ind << "uint64_t a" << k << "[4];\n" << ind << "load_value_k<" << (int)F.kind << ">(" << col_expr(F.col)
+              << ", row, a" << k << ");\n";
     } else if (F.kind == spec::K_MESSAGE || F.kind == spec::K_LIST)
-        o << ind << "const uint32_t pr" << k << sfx << " = ((const uint8_t *)" << col_expr(F.present) << ")[" << rv << "];\n";
-    if (F.kind == spec::K_MESSAGE) o << ind << "const uint32_t sz" << k << sfx << " = B.size[" << F.table << "][" << rv << "];\n";
+        o << ind << "const uint32_t pr" << k << " = ((const uint8_t *)" << col_expr(F.present) << ")[row];\n";
+    if (F.kind == spec::K_MESSAGE) o << ind << "const uint32_t sz" << k << " = B.size[" << F.table << "][row];\n";
     // a struct's member values (every scalar member of its subtree: gen_struct_emit)
     if (F.kind == spec::K_STRUCT && eager) {
         const uint32_t fi = D.direct[T.d0 + k];
         for (uint32_t i = fi + 1; i < F.send; i++)
             if (D.f[i].kind != spec::K_STRUCT)
-                o << ind << "uint64_t m" << i << sfx << "[4];\n" << ind << "load_value_k<" << (int)D.f[i].kind << ">("
-                  << col_expr(D.f[i].col) << ", " << rv << ", m" << i << sfx << ");\n";
+                o << ind << "uint64_t m" << i << "[4];\n" << ind << "load_value_k<" << (int)D.f[i].kind << ">("
+                  << col_expr(D.f[i].col) << ", row, m" << i << ");\n";
     }
     // a list's element range [begin[row], begin[row + 1]) (the size pass checked BEGIN)
     if (F.kind == spec::K_LIST)
-        o << ind << "const uint32_t j0_" << k << sfx << " = ((const uint32_t *)" << col_expr(D.t[F.table].begin_col) << ")[" << rv
-          << "], j1_" << k << sfx << " = ((const uint32_t *)" << col_expr(D.t[F.table].begin_col) << ")[" << rv << " + 1];\n";
-}
-
-// binds gen_field_loads' suffixed variables of field k to the names gen_field_write reads
-void gen_field_bind(std::ostringstream &o, const TreeDesc &D, const TTable &T, uint32_t k, const std::string &sfx,
-                    const char *ind) {
-    const TField &F = D.f[D.direct[T.d0 + k]];
-    if ((F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) || F.kind == spec::K_ANY)
-        o << ind << "uint64_t (&a" << k << ")[4] = a" << k << sfx << ";\n";
-    else if (F.kind == spec::K_MESSAGE || F.kind == spec::K_LIST)
-        o << ind << "const uint32_t pr" << k << " = pr" << k << sfx << ";\n";
-    if (F.kind == spec::K_MESSAGE) o << ind << "const uint32_t sz" << k << " = sz" << k << sfx << ";\n";
-    if (F.kind == spec::K_LIST)
-        o << ind << "const uint32_t j0_" << k << " = j0_" << k << sfx << ", j1_" << k << " = j1_" << k << sfx << ";\n";
-    if (F.kind == spec::K_STRUCT) {
-        const uint32_t fi = D.direct[T.d0 + k];
-        for (uint32_t i = fi + 1; i < F.send; i++)
-            if (D.f[i].kind != spec::K_STRUCT) o << ind << "uint64_t (&m" << i << ")[4] = m" << i << sfx << ";\n";
-    }
+        o << ind << "const uint32_t j0_" << k << " = ((const uint32_t *)" << col_expr(D.t[F.table].begin_col) << ")[row], j1_" << k
+          << " = ((const uint32_t *)" << col_expr(D.t[F.table].begin_col) << ")[row + 1];\n";
 }
 
 // struct field sf's EncodeXxxTo (internal/lang/generator/struct.go:115-142) from its loaded
@@ -1311,14 +1223,14 @@ void gen_pair_rows(std::ostringstream &o, const TreeDesc &D, uint32_t x, int P) 
 constexpr int TILE_W = spec::TREE_TILE_W;
 
 bool tree_tile(const TreeDesc &D) {
-    if (!SPEC_AB_TREE_TILE || D.ntables > 32 || D.t[0].shape != spec::SHAPE_MESSAGE) return false;
+    if (D.ntables > 32 || D.t[0].shape != spec::SHAPE_MESSAGE) return false;
     for (uint32_t t = 0; t < D.ntables; t++)
         if (D.t[t].shape == spec::SHAPE_MESSAGE && D.t[t].nd > 64) return false;
     return true;
 }
 
-// a records' field's share of its wave's time in the tile writer, in scalar fields (fitted to the
-// per-wave clocks of a -DSPEC_AB_TILE_CLOCK=1 build on pkg1: a list ≈ 5, a string ≈ 2)
+// a records' field's share of its wave's time in the tile writer, in scalar fields (fitted to
+// per-wave clocks measured on pkg1: a list ≈ 5, a string ≈ 2)
 uint32_t tile_field_cost(const TreeDesc &D, const TField &F) {
     switch (F.kind) {
     case spec::K_STRING: case spec::K_BYTES: case spec::K_ANY: return 2;
@@ -1349,96 +1261,6 @@ void tile_cuts(const TreeDesc &D, uint32_t *cut) {
         cut[b + 1] = k;
     }
     cut[TILE_W] = T.nd;
-}
-
-// A table whose tile rows at one depth run in ROUNDS (SPEC_AB_TILE_ROUNDS): each thread issues the
-// reads of its next row of every such table at once, then writes them one after another — a
-// thread holds about one row per table per tile, so per-table loops were one dependent chain of
-// reads per table.  Message tables, lists of scalars / strings / bytes, lists of structs.
-bool tile_round_ok(const TreeDesc &D, uint32_t x) {
-    const TTable &X = D.t[x];
-    if (!SPEC_AB_TILE_ROUNDS) return false;
-    if (X.shape == spec::SHAPE_MESSAGE || X.shape == spec::SHAPE_STRUCT) return true;
-    return X.shape == spec::SHAPE_VALUE && D.f[X.field].elem >= spec::K_BOOL && D.f[X.field].elem <= spec::K_BYTES;
-}
-
-// the reads of row `rv` of table x (round mode) into variables suffixed sfx: declarations
-// (zeroed) into decl, the reads, under the row's validity, into rd
-void gen_round_loads(std::ostringstream &decl, std::ostringstream &rd, const TreeDesc &D, uint32_t x,
-                     const std::string &sfx, const std::string &rv) {
-    const TTable &X = D.t[x];
-    auto member_loads = [&](uint32_t sf) {
-        for (uint32_t i = sf + 1u; i < D.f[sf].send; i++)
-            if (D.f[i].kind != spec::K_STRUCT) {
-                decl << "    uint64_t m" << i << sfx << "[4] = {0, 0, 0, 0};\n";
-                rd << "      load_value_k<" << (int)D.f[i].kind << ">(" << col_expr(D.f[i].col) << ", " << rv << ", m" << i << sfx
-                   << ");\n";
-            }
-    };
-    decl << "    uint64_t start" << sfx << " = ~0ull;\n";
-    rd << "      start" << sfx << " = B.pos[" << x << "][" << rv << "];\n";
-    if (X.shape == spec::SHAPE_VALUE) {
-        const TField &F = D.f[X.field];
-        decl << "    uint64_t a" << sfx << "[4] = {0, 0, 0, 0};\n";
-        rd << "      load_value_k<" << (int)F.elem << ">(" << col_expr(F.col) << ", " << rv << ", a" << sfx << ");\n";
-        return;
-    }
-    if (X.shape == spec::SHAPE_STRUCT) {
-        member_loads(X.field);
-        return;
-    }
-    for (uint32_t k = 0; k < X.nd; k++) {
-        const uint32_t fi = D.direct[X.d0 + k];
-        const TField &F = D.f[fi];
-        const std::string ks = std::to_string(k);
-        if ((F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) || F.kind == spec::K_ANY) {
-            decl << "    uint64_t a" << k << sfx << "[4] = {0, 0, 0, 0};\n";
-            rd << "      load_value_k<" << (int)F.kind << ">(" << col_expr(F.col) << ", " << rv << ", a" << k << sfx << ");\n";
-        } else if (F.kind == spec::K_MESSAGE || F.kind == spec::K_LIST) {
-            decl << "    uint32_t pr" << k << sfx << " = 0;\n";
-            rd << "      pr" << k << sfx << " = ((const uint8_t *)" << col_expr(F.present) << ")[" << rv << "];\n";
-        }
-        if (F.kind == spec::K_MESSAGE) {
-            decl << "    uint32_t sz" << k << sfx << " = 0;\n";
-            rd << "      sz" << k << sfx << " = B.size[" << F.table << "][" << rv << "];\n";
-        }
-        if (F.kind == spec::K_LIST) {
-            const std::string bc = "((const uint32_t *)" + col_expr(D.t[F.table].begin_col) + ")";
-            decl << "    uint32_t j0_" << k << sfx << " = 0, j1_" << k << sfx << " = 0;\n";
-            rd << "      j0_" << k << sfx << " = " << bc << "[" << rv << "];\n      j1_" << k << sfx << " = " << bc << "[" << rv
-               << " + 1];\n";
-        }
-        if (F.kind == spec::K_STRUCT) member_loads(fi);
-    }
-}
-
-// the write of the row read by gen_round_loads (valid, placed)
-void gen_round_write(std::ostringstream &o, const TreeDesc &D, uint32_t x, const std::string &sfx, const std::string &rv) {
-    const TTable &X = D.t[x];
-    o << "      {\n      const uint64_t row = " << rv << ", start = start" << sfx << ";\n      (void)row;\n";
-    if (X.shape == spec::SHAPE_VALUE) {
-        const TField &F = D.f[X.field];
-        const bool heap = F.elem == spec::K_STRING || F.elem == spec::K_BYTES;
-        o << "      if (start != ~0ull) {\n      auto em = mk(start);\n      emit_value_k<" << (int)F.elem << ">(em, a" << sfx << ", "
-          << (heap ? "B.heaps[" + std::to_string(F.col) + "], B.heap_lens[" + std::to_string(F.col) + "]" : "nullptr, 0")
-          << ");\n      em.finish();\n      }\n      }\n";
-        return;
-    }
-    if (X.shape == spec::SHAPE_STRUCT) {
-        for (uint32_t i = X.field + 1u; i < D.f[X.field].send; i++)
-            if (D.f[i].kind != spec::K_STRUCT) o << "      uint64_t (&m" << i << ")[4] = m" << i << sfx << ";\n";
-        o << "      if (start != ~0ull) {\n      auto em = mk(start);\n";
-        gen_struct_emit(o, D, X.field, 0, "      ");
-        o << "      em.finish();\n      }\n      }\n";
-        return;
-    }
-    for (uint32_t k = 0; k < X.nd; k++) gen_field_bind(o, D, X, k, sfx, "      ");
-    o << "      if (start == ~0ull) {\n        gen_unplace_" << x << "(D, B, row);\n      } else {\n"
-      << "      auto em = mk(start);\n      uint32_t nf = 0;\n      bool bigtag = false;\n";
-    for (uint32_t k = 0; k < X.nd; k++) gen_field_write(o, D, X, k, true);
-    o << "  const uint64_t data = em.pos - start;\n  const bool big = bigtag || (nf > 0 && data > 65535);\n";
-    gen_table_trailer(o, D, X);
-    o << "      }\n      }\n";
 }
 
 void gen_tile(std::ostringstream &o, const TreeDesc &D) {
@@ -1537,11 +1359,9 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
     o << "template <class Mk>\n__device__ __forceinline__ void gen_tile_body(const Mk &mk, const TreeDesc &D, const TreeBufs &B, "
          "uint64_t r0, uint64_t r1) {\n"
       << "  const uint64_t row = r0 + (threadIdx.x & 63);\n"
-      << (SPEC_AB_TILE_CLOCK ? "  const uint64_t c0 = wall_clock64();\n" : "")
       << "  if (row < r1) switch (threadIdx.x >> 6) {\n";
     for (int b = 0; b < TILE_W; b++) o << "  case " << b << ": gen_troot_" << b << "(mk, D, B, row); break;\n";
     o << "  }\n  __syncthreads();\n  const uint64_t lo0 = r0, hi0 = r1;\n";
-    if (SPEC_AB_TILE_CLOCK) o << "  if (threadIdx.x == 0) { B.tmask[r0] = c0; B.tmask[r0 + 1] = wall_clock64(); }\n";
     for (uint32_t x = 1; x < D.ntables; x++) {
         const TTable &X = D.t[x];
         // (an owner range that is empty reads no BEGIN: the column may be absent then)
@@ -1553,41 +1373,17 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
         else
             o << "  const uint64_t lo" << x << " = lo" << X.parent << ", hi" << x << " = hi" << X.parent << ";\n";
     }
-    // depth d: the tables' row ranges laid end to end, index i to thread i mod blockDim; the
-    // tables of tile_round_ok in rounds (every such table's next row of this thread read at once),
-    // the others in one loop per table over this thread's indices in its segment (an if-chain
-    // over the tables inside one loop took the register coalescer minutes)
+    // depth d: the tables' row ranges laid end to end, index i to thread i mod blockDim, one
+    // loop per table over this thread's indices in its segment (an if-chain over the tables
+    // inside one loop took the register coalescer minutes)
     for (int d = 1; d <= maxd; d++) {
         o << "  { // depth " << d << "\n    uint64_t base = 0;\n";
-        std::vector<uint32_t> rt;
         for (uint32_t x = 1; x < D.ntables; x++)
-            if (depth[x] == d) {
-                o << "    const uint64_t c" << x << " = hi" << x << " - lo" << x << ", b" << x << " = base;\n    base += c" << x << ";\n";
-                if (tile_round_ok(D, x)) rt.push_back(x);
-                else
-                    o << "    for (uint64_t i = (uint32_t)(threadIdx.x - b" << x << ") % blockDim.x; i < c" << x
-                      << "; i += blockDim.x)\n      gen_trow_" << x << "(mk, D, B, lo" << x << " + i);\n";
-            }
-        if (!rt.empty()) {
-            o << "    for (uint64_t r = 0;; r += blockDim.x) {\n";
-            std::ostringstream decl, rd, wr;
-            for (uint32_t x : rt) {
-                const std::string sx = "_t" + std::to_string(x), rv = "rw" + std::to_string(x);
-                o << "    const uint64_t j" << x << " = (uint32_t)(threadIdx.x - b" << x << ") % blockDim.x + r;\n"
-                  << "    const bool v" << x << " = j" << x << " < c" << x << ";\n"
-                  << "    const uint64_t " << rv << " = lo" << x << " + j" << x << ";\n";
-                rd << "      if (v" << x << ") {\n";
-                gen_round_loads(decl, rd, D, x, sx, rv);
-                rd << "      }\n";
-                wr << "      if (v" << x << ") \n";
-                gen_round_write(wr, D, x, sx, rv);
-            }
-            o << "    if (!(false";
-            for (uint32_t x : rt) o << " || v" << x;
-            o << ")) break;\n" << decl.str() << rd.str() << wr.str() << "    }\n";
-        }
+            if (depth[x] == d)
+                o << "    const uint64_t c" << x << " = hi" << x << " - lo" << x << ", b" << x << " = base;\n    base += c" << x << ";\n"
+                  << "    for (uint64_t i = (uint32_t)(threadIdx.x - b" << x << ") % blockDim.x; i < c" << x
+                  << "; i += blockDim.x)\n      gen_trow_" << x << "(mk, D, B, lo" << x << " + i);\n";
         o << "    (void)base;\n  }\n  __syncthreads();\n";
-        if (SPEC_AB_TILE_CLOCK) o << "  if (threadIdx.x == 0) B.tmask[r0 + " << d + 1 << "] = wall_clock64();\n";
     }
     o << "}\n"
       << "extern \"C\" __global__ __launch_bounds__(" << TILE_W * 64
@@ -1604,16 +1400,16 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
       << "  const uint64_t org = B.offsets[r0] - B.frame_head, fin = B.offsets[r1 - 1] + B.size[0][r1 - 1];\n"
       // (out + sh 16-byte aligned: the image's chunks are the output's)
       << "  const uint64_t sh = org - (((unsigned long long)B.out + org) & 15);\n"
-      << (SPEC_AB_TILE_OR ? "  tile_clear(img, fin - sh < cap ? (uint32_t)(fin - sh) : cap);\n  __syncthreads();\n" : "")
+      // (the image starts zeroed: the rows OR their dwords into it, tree_core.hpp LSink::word)
+      << "  tile_clear(img, fin - sh < cap ? (uint32_t)(fin - sh) : cap);\n  __syncthreads();\n"
       << "  gen_tile_body(MkL{img, B.out, sh, cap}, D, B, r0, r1);\n"
       << "  tile_copy_out(B.out, img, sh, org, fin < sh + cap ? fin : sh + cap);\n"
-      << (SPEC_AB_TILE_CLOCK ? "  __syncthreads();\n  if (threadIdx.x == 0) B.tmask[r0 + 63] = wall_clock64();\n" : "")
       << "}\n";
 }
 
 std::string generate_tree(const TreeDesc &D, bool *has) {
     std::ostringstream o;
-    o << (SPEC_AB_TILE_OR ? "#define SPEC_TILE_OR 1\n" : "") << "#include \"tree_decode_core.hpp\"\nusing namespace spec;\n";
+    o << "#include \"tree_decode_core.hpp\"\nusing namespace spec;\n";
     for (uint32_t t = 0; t < D.ntables; t++)
         if (D.t[t].shape == spec::SHAPE_MESSAGE) {
             gen_write_table(o, D, t);
@@ -1659,7 +1455,7 @@ std::string generate_tree(const TreeDesc &D, bool *has) {
       << "      if (total > 0xffffffffull) err = true;\n"
       << "      B.size[x][row] = (uint32_t)total;\n"
       << "    }\n  }\n  if (err) *B.err = 1;\n}\n";
-    // the level-fused writer: where the record-tile writer does not apply (or is switched off)
+    // the level-fused writer: where the record-tile writer does not apply
     if (!tree_tile(D)) {
         o << "extern \"C\" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void spec_tree_write_set("
              "const TreeDesc *Dp, const TreeBufs *Bp, TableSet s) {\n"
@@ -1778,12 +1574,7 @@ std::string generate_tree(const TreeDesc &D, bool *has) {
 
 struct TreeEntry {
     hipModule_t mod = nullptr;
-    // [x]: decode, staged rows; [TREE_MAX_T + x]: decode, rows from HBM; [2 TREE_MAX_T + x]:
-    // decode on 2 waves per 64 rows (the root group, gen_pair_rows; nullptr if not split);
-    // [4 TREE_MAX_T], [+1]: the
-    // level-fused encode size / write kernels; [+2]: the level-fused list-group decode kernel;
-    // [+3]: the record-tile writer (nullptr where gen_tile does not apply)
-    hipFunction_t fn[4 * spec::TREE_MAX_T + 4] = {};
+    hipFunction_t fn[spec::TREE_FN_COUNT] = {}; // by tree_internal.hpp TreeFn
     bool failed = false;
 };
 std::unordered_map<std::string, TreeEntry> g_tree_cache;
@@ -1800,13 +1591,9 @@ long long jit_compile_only_tree(const TreeDesc &D) {
     return (long long)compile_source(src, TREE).size();
 }
 
-// The schema-specialised group kernels of a tree: fn[x] for each group root x that has one
-// (nullptr where the run-time kernel runs), fn[TREE_MAX_T + x] its variant without staging,
-// fn[2 TREE_MAX_T + x] its 2-wave variant (root group only; nullptr when not split),
-// fn[4 TREE_MAX_T] / fn[4 TREE_MAX_T + 1] the level-fused size / write kernels of the encoder,
-// fn[4 TREE_MAX_T + 2] the level-fused list-group decode kernel, fn[4 TREE_MAX_T + 3] the
-// record-tile writer (one of the two writers is generated: nullptr for the other); nullptr
-// when the JIT is off or failed.
+// The kernels of a tree's generated module by tree_internal.hpp TreeFn: a group kernel for each
+// group root that has one (nullptr where the run-time kernel runs), one of the encoder's two
+// writers (nullptr for the other); nullptr when the JIT is off or failed.
 const hipFunction_t *jit_tree_kernels(const TreeDesc &D) {
     if (!enabled()) return nullptr;
     int dev = 0;
@@ -1833,20 +1620,19 @@ const hipFunction_t *jit_tree_kernels(const TreeDesc &D) {
         TreeEntry e;
         const std::vector<char> code = compile_source(src, TREE);
         bool ok = !code.empty() && hipModuleLoadData(&e.mod, code.data()) == hipSuccess;
+        auto get = [&](int fn, const std::string &name) {
+            return hipModuleGetFunction(&e.fn[fn], e.mod, name.c_str()) == hipSuccess;
+        };
         if (ok)
-            ok = hipModuleGetFunction(&e.fn[4 * TREE_MAX_T], e.mod, "spec_tree_size_set") == hipSuccess &&
-                 hipModuleGetFunction(&e.fn[4 * TREE_MAX_T + 2], e.mod, "spec_tree_group_set") == hipSuccess &&
-                 hipModuleGetFunction(&e.fn[4 * TREE_MAX_T + (tree_tile(D) ? 3 : 1)], e.mod,
-                                      tree_tile(D) ? "spec_tree_write_tile" : "spec_tree_write_set") == hipSuccess;
+            ok = get(TREE_FN_SIZE_SET, "spec_tree_size_set") && get(TREE_FN_GROUP_SET, "spec_tree_group_set") &&
+                 (tree_tile(D) ? get(TREE_FN_WRITE_TILE, "spec_tree_write_tile") : get(TREE_FN_WRITE_SET, "spec_tree_write_set"));
         for (uint32_t x = 0; ok && x < D.ntables; x++) {
             if (!has[x]) continue;
             const std::string name = "spec_tree_group_" + std::to_string(x);
-            ok = hipModuleGetFunction(&e.fn[x], e.mod, name.c_str()) == hipSuccess &&
-                 hipModuleGetFunction(&e.fn[TREE_MAX_T + x], e.mod, (name + "g").c_str()) == hipSuccess;
+            ok = get(TREE_FN_GROUP + x, name) && get(TREE_FN_GROUP_HBM + x, name + "g");
             std::vector<char> sel[4];
             uint32_t tw[TREE_MAX_T];
-            if (ok && x == 0 && pair_split(D, x, 2, sel, tw))
-                ok = hipModuleGetFunction(&e.fn[2 * TREE_MAX_T + x], e.mod, (name + "p2").c_str()) == hipSuccess;
+            if (ok && x == 0 && pair_split(D, x, 2, sel, tw)) ok = get(TREE_FN_GROUP_PAIR + x, name + "p2");
         }
         if (!ok) {
             (void)hipGetLastError();
@@ -1880,37 +1666,19 @@ int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, doubl
     if (decode_slab_bytes(avg_record) == 0) return 0; // records too large for LDS: generic kernel
     const Entry *ent = lookup(schema, DECODE);
     if (!ent) return 0;
-    hipFunction_t fn = ent->fn[a.f.errmask ? 1 : 0]; // the errmask variant for spec_decode_flat_errors
     if (a.n <= a.r0) return 1;
-    const bool wide = schema->nfields > (uint32_t)FAST_MAX_FIELDS || [&] {
-        for (uint32_t f = 0; f < schema->nfields; f++)
-            if (schema->fields[f].tag > 255) return true;
-        return false;
-    }();
-    if (flat_pair() >= (wide ? 1 : 2) && ent->fn[a.f.errmask ? 3 : 2] && !persistent_decode()) {
-        // a wave pair per 64 records, one slab per pair (+ 256 B exchange, + 512 B of masks)
-        DecodeArgs args = a;
-        args.slab = decode_slab_bytes(avg_record);
-        args.xcd = xcd_swizzle_decode();
-        uint64_t groups = (a.n - a.r0 + 63) / 64;
-        if (args.xcd) groups = (groups + 7) / 8 * 8;
-        size_t size = sizeof(args);
-        void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
-                         HIP_LAUNCH_PARAM_END};
-        hipError_t e = hipModuleLaunchKernel(ent->fn[a.f.errmask ? 3 : 2], (unsigned)groups, 1, 1,
-                                             64 * SPEC_AB_FLAT_WAVES, 1, 1,
-                                             args.slab + (SPEC_AB_FLAT_WAVES - 1) * (a.f.errmask ? 768 : 256), stream,
-                                             nullptr, extra);
-        return e == hipSuccess ? 1 : -1;
-    }
-    const DecodeLaunch L = decode_launch(a.n - a.r0, avg_record, device_cus(), persistent_decode(), decode_wpb());
+    // a wave pair per 64 records, one slab per pair (+ 256 B exchange, + 512 B of masks), the
+    // groups in 8 equal XCD shares
     DecodeArgs args = a;
-    args.slab = L.slab;
-    args.xcd = xcd_swizzle_decode() && !persistent_decode();
+    args.slab = decode_slab_bytes(avg_record);
+    args.xcd = 1;
+    const uint64_t groups = ((a.n - a.r0 + 63) / 64 + 7) / 8 * 8;
     size_t size = sizeof(args);
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
-    hipError_t e = hipModuleLaunchKernel(fn, L.blocks, 1, 1, 64 * L.wpb, 1, 1, L.lds, stream, nullptr, extra);
+    hipError_t e = hipModuleLaunchKernel(ent->fn[a.f.errmask ? DEC_PAIR_ERR : DEC_PAIR], (unsigned)groups, 1, 1,
+                                         64 * FLAT_WAVES, 1, 1,
+                                         args.slab + (FLAT_WAVES - 1) * (a.f.errmask ? 768 : 256), stream, nullptr, extra);
     return e == hipSuccess ? 1 : -1;
 }
 
@@ -1921,18 +1689,10 @@ int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write
     size_t size = sizeof(args);
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
-    hipError_t rc;
-    if (write && a.frame_head) { // the framed write pass: never the pair kernel, which knows no head
-        rc = hipModuleLaunchKernel(e->fn[3], (unsigned)a.nblocks, 1, 1, ENC_BLOCK, 1, 1,
-                                   (unsigned)enc_write_lds_bytes(), stream, nullptr, extra);
-    } else if (write && e->fn[2]) { // the write pass on wave pairs (encode_write_pair_body)
-        const int h = enc_pair_split(schema);
-        rc = hipModuleLaunchKernel(e->fn[2], (unsigned)a.nblocks, 1, 1, ENC_PAIR_BLOCK, 1, 1,
-                                   (unsigned)enc_pair_lds_bytes(h), stream, nullptr, extra);
-    } else {
-        rc = hipModuleLaunchKernel(e->fn[write ? 1 : 0], (unsigned)a.nblocks, 1, 1, ENC_BLOCK, 1, 1,
-                                   write ? (unsigned)enc_write_lds_bytes() : 0, stream, nullptr, extra);
-    }
+    // (the framed write pass, a.frame_head: the framed instantiation of the same kernel)
+    const int which = !write ? ENC_SIZE : a.frame_head ? ENC_WRITE_FRAMES : ENC_WRITE;
+    hipError_t rc = hipModuleLaunchKernel(e->fn[which], (unsigned)a.nblocks, 1, 1, ENC_BLOCK, 1, 1,
+                                          write ? (unsigned)enc_write_lds_bytes() : 0, stream, nullptr, extra);
     return rc == hipSuccess ? 1 : -1;
 }
 
@@ -1950,28 +1710,12 @@ int jit_launch_nested(const spec_nested_schema *schema, const NestedArgs &a, int
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
     unsigned grid = (unsigned)((a.n + 63) / 64);
-    if (args.xcd && mode != NESTED_ONEPASS) grid = (grid + 7) / 8 * 8; // 8 equal XCD shares
-    else args.xcd = 0;
-    size_t lds = a.slab + (mode == NESTED_RANGES ? NESTED_RANGE_BYTES : 0u);
-    unsigned threads = 64;
-    if (mode == NESTED_GROUPS && nested_pair() && e->fn[3]) { // a wave pair per group (nested_decode_pair)
-        mode = 3;
-        threads = 64 * SPEC_AB_NESTED_WAVES;
-        lds = a.slab + 1024; // the posted lists: 4 words per record
-    }
-    if (mode == NESTED_PAIR_ONEPASS) { // a wave pair per group, one look-back per group, block order
-        if (!e->fn[4]) return 0;
-        args.xcd = 0;
-        hipError_t rc = hipModuleLaunchKernel(e->fn[4], (unsigned)((a.n + 63) / 64), 1, 1, 64 * SPEC_AB_NESTED_WAVES, 1,
-                                              1, a.slab + 1024 + 16, stream, nullptr, extra);
-        return rc == hipSuccess ? 1 : -1;
-    }
-    if (mode == NESTED_ONEPASS) { // DEC_WAVES groups per block: one look-back per block
-        grid = (grid + DEC_WAVES - 1) / DEC_WAVES;
-        threads = 64 * DEC_WAVES;
-        lds *= DEC_WAVES;
-    }
-    hipError_t rc = hipModuleLaunchKernel(e->fn[mode], grid, 1, 1, threads, 1, 1, (unsigned)lds, stream, nullptr, extra);
+    if (args.xcd) grid = (grid + 7) / 8 * 8; // 8 equal XCD shares
+    const bool ranges = mode == NESTED_RANGES; // a wave per group; else a wave pair (nested_decode_pair)
+    // LDS: the slab, then the ranges' window or the pair's posted lists (4 words per record)
+    const size_t lds = a.slab + (ranges ? NESTED_RANGE_BYTES : 1024u);
+    hipError_t rc = hipModuleLaunchKernel(e->fn[ranges ? NEST_RANGES : NEST_PAIR], grid, 1, 1,
+                                          ranges ? 64 : 64 * NESTED_WAVES, 1, 1, (unsigned)lds, stream, nullptr, extra);
     return rc == hipSuccess ? 1 : -1;
 }
 
@@ -1980,24 +1724,23 @@ long long jit_compile_only_nested_encode(const spec_nested_schema *schema) {
     return (long long)compile_source(generate_nested_encode(schema), NESTED_ENC).size();
 }
 
-#ifndef SPEC_AB_NENC_PAIR
-#define SPEC_AB_NENC_PAIR 1
-#endif
 int jit_launch_nested_encode(const spec_nested_schema *schema, const NestedEncodeArgs &a, bool write,
                              hipStream_t stream) {
     const Entry *e = lookup_nested_encode(schema);
     if (!e) return 0;
     NestedEncodeArgs args = a;
-    args.xcd = write && xcd_swizzle_decode() ? 1u : 0u;
+    args.xcd = write ? 1u : 0u;
     size_t size = sizeof(args);
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
     const unsigned lds = (unsigned)(write ? nenc_write_lds_bytes() : nenc_size_lds_bytes());
     const unsigned grid = (unsigned)(args.xcd ? (a.nblocks + 7) / 8 * 8 : a.nblocks);
     // the write pass on wave pairs when the size pass left its item prefixes (nested_enc_write_pair_body)
-    const bool pair = write && SPEC_AB_NENC_PAIR && e->fn[2] && a.item_pre && a.wave_ok;
+    const bool pair = write && e->fn[NENC_WRITE_PAIR] && a.item_pre && a.wave_ok;
     // (the framed write pass, a.frame_head: the framed instantiation of the same kernel)
-    const int which = !write ? 0 : a.frame_head ? (pair ? 4 : 3) : (pair ? 2 : 1);
+    const int which = !write         ? NENC_SIZE
+                      : a.frame_head ? (pair ? NENC_WRITE_PAIR_FRAMES : NENC_WRITE_FRAMES)
+                                     : (pair ? NENC_WRITE_PAIR : NENC_WRITE);
     hipError_t rc = hipModuleLaunchKernel(e->fn[which], grid, 1, 1, pair ? 2 * NENC_BLOCK : NENC_BLOCK, 1, 1, lds, stream,
                                           nullptr, extra);
     return rc == hipSuccess ? 1 : -1;

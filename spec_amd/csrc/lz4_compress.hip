@@ -50,15 +50,6 @@ constexpr uint32_t LANE_LIT = 16;                        // literal runs a lane 
 constexpr uint32_t STEP_SEQS = 64 / MIN_MATCH;           // sequences a step can start
 constexpr uint32_t SCAN_CHUNK = 1024;                    // blocks per pass of the scan
 
-// Test builds with one deliberate fault each (make HIPFLAGS+="-DSPEC_AB_LZ4C_FAULT=k"; DESIGN.md §8
-// says which test catches which): 1 the stored bit left clear, 2 the end-of-block clamp off by
-// one, 3 the pack pass writing a full 16 bytes at a record's tail (over a resource that reaches
-// the bound), 4 matches never taken.
-#ifndef SPEC_AB_LZ4C_FAULT
-#define SPEC_AB_LZ4C_FAULT 0
-#endif
-constexpr int FAULT = SPEC_AB_LZ4C_FAULT;
-
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(64) void lz4c_block_kernel(CompressArgs a) {
         const uint32_t d = p + 1 - t; // t <= p: an earlier step's position
         const uint32_t c = p - d;
         bool has = t != 0 && d <= MAX_OFFSET && d <= p && p < mfl && p >= anchor;
-        if (has) has = in.get32(c) == cur && FAULT != 4;
+        if (has) has = in.get32(c) == cur;
         uint64_t mask = __ballot(has);
         if (!mask) continue;
         // every lane extends its own match by up to LANE_ROUNDS dwords (to 4 + 4 * LANE_ROUNDS = 32 bytes)
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(64) void lz4c_block_kernel(CompressArgs a) {
                     m += 256;
                 }
             }
-            m = clamp_match(pk, m, FAULT == 2 ? n + 1 : n);
+            m = clamp_match(pk, m, n);
             uint32_t past = pk + 1; // (a match the clamp leaves nothing of: cannot happen below mfl)
             if (m) {
                 if (lane == k) {
@@ -210,7 +201,7 @@ __global__ __launch_bounds__(64) void lz4c_block_kernel(CompressArgs a) {
         if (lane == 0) put_head(out, o, ll, 0);
         wave_copy(out, o + 1 + lit_ext_bytes(ll), in, anchor, ll, lane);
     }
-    if (lane == 0) a.words[b] = FAULT == 1 ? block_word(csize, n) & ~STORED_BIT : block_word(csize, n);
+    if (lane == 0) a.words[b] = block_word(csize, n);
 }
 
 // offsets[k] = where block k's size word goes in the frame; offsets[nblocks] = the blocks' end
@@ -280,14 +271,14 @@ __global__ __launch_bounds__(256) void lz4c_pack_kernel(PackArgs a) {
     }
     const uint32_t n = block_len(a.len, a.block_max, b);
     const uint32_t word = a.words[b];
-    const bool stored = FAULT == 1 ? word == n : word >> 31;
+    const bool stored = word >> 31;
     uint32_t sz = word & ~STORED_BIT;
     if (sz > n) sz = n; // what the block kernel writes is never larger
     const BufIn src{stored ? uniform_rsrc(a.data + b * (uint64_t)a.block_max, n) : uniform_rsrc(a.slots + b * a.slot, a.slot),
                     stored ? n : (uint32_t)a.slot};
     const uint64_t at = a.offsets[b];
     const uint32_t rec = 4 + sz; // record byte j: the size word, then payload byte j - 4
-    const BufOut dst = out_region(a, at, FAULT == 3 ? a.bound : rec);
+    const BufOut dst = out_region(a, at, rec);
     auto byte_at = [&](uint32_t j) -> uint32_t { return j < 4 ? (word >> (8 * j)) & 0xff : src.get(j - 4); };
     // up to the output's first 16-byte boundary past the size word
     uint32_t head = (16 - (uint32_t)(((uintptr_t)a.out + at) & 15)) & 15;
@@ -309,7 +300,7 @@ __global__ __launch_bounds__(256) void lz4c_pack_kernel(PackArgs a) {
         }
     }
     const uint32_t done = head + 16 * granules;
-    if (t < (FAULT == 3 ? 16 : rec - done)) dst.put(done + t, byte_at(done + t));
+    if (t < rec - done) dst.put(done + t, byte_at(done + t));
 }
 
 } // namespace

@@ -13,37 +13,11 @@
 
 namespace spec {
 
-// Build-time A/B (make HIPFLAGS+="-DSPEC_AB_TREE_TILE=0"): 1 generates the tree encoder's
-// record-tile writer (jit.cpp gen_tile) where it applies, 0 the level-fused write sets always.
-#ifndef SPEC_AB_TREE_TILE
-#define SPEC_AB_TREE_TILE 1
-#endif
-// the tile writer's waves per workgroup (= field blocks of the records' table) and waves per SIMD
-// (its register budget): 4 WPE / W workgroups per CU share the LDS, per workgroup the image of
-// the tile's output range and a dummy dword
-#ifndef SPEC_AB_TREE_TILE_W
-#define SPEC_AB_TREE_TILE_W 4
-#endif
-#ifndef SPEC_AB_TREE_TILE_WPE
-#define SPEC_AB_TREE_TILE_WPE 4 // waves per SIMD the kernel is compiled for (amdgpu_waves_per_eu)
-#endif
-constexpr int TREE_TILE_W = SPEC_AB_TREE_TILE_W, TREE_TILE_WPE = SPEC_AB_TREE_TILE_WPE;
-// measurement build (-DSPEC_AB_TILE_CLOCK=1, tools/tile_clock.py): each tile's workgroup stores the
-// wall clock at its phase boundaries over its records' B.tmask entries (read back from the workspace)
-#ifndef SPEC_AB_TILE_CLOCK
-#define SPEC_AB_TILE_CLOCK 0
-#endif
-// the tile writer's rows below the records in rounds over the tables of a depth (jit.cpp
-// tile_round_ok); 0: one loop per table.  Measured on pkg1: depth-1 phase 24.0 vs 23.7 us per
-// tile (tools/tile_clock.py), encode 0.2864 vs 0.2844 ms — no gain, off
-#ifndef SPEC_AB_TILE_ROUNDS
-#define SPEC_AB_TILE_ROUNDS 0
-#endif
-// the tile writer's LDS image starts zeroed and rows OR their dwords into it (tree_core.hpp
-// LSink::word), so the emitter's stores need no edge cases
-#ifndef SPEC_AB_TILE_OR
-#define SPEC_AB_TILE_OR 1
-#endif
+// The tree encoder's record-tile writer (jit.cpp gen_tile): waves per workgroup (= field blocks of
+// the records' table) and waves per SIMD the kernel is compiled for (amdgpu_waves_per_eu, its
+// register budget): 4 WPE / W workgroups per CU share the LDS, per workgroup the image of the
+// tile's output range and a dummy dword
+constexpr int TREE_TILE_W = 4, TREE_TILE_WPE = 4;
 constexpr uint32_t TREE_TILE_IMG = ((163840u / (4u * TREE_TILE_WPE / TREE_TILE_W)) - 32u) & ~15u;
 
 // encode_nested.hip
@@ -79,28 +53,19 @@ void note_hip_error(hipError_t e); // capi.hip: remembered for spec_last_hip_err
 // capi.hip: bytes copied to the device on st from a pooled pinned slot of the current device (no
 // host wait: the pool grows while every slot's copy is in flight; not graph-capturable)
 hipError_t pinned_upload(void *dst, const void *src, size_t bytes, hipStream_t st);
-bool persistent_decode(); // build-time A/B variants (decode_flat.hip): SPEC_AB_PERSIST
-unsigned decode_wpb();     // SPEC_AB_WPB (waves per block, default 1)
-int flat_pair();
-bool nested_pair(); // decode_nested.hip: SPEC_AB_NESTED_PAIR           // SPEC_AB_FLAT_PAIR: 1 wide schemas / 2 every schema on wave pairs (decode_flat_pair)
 int launch_parse(DecodeArgs a, uint32_t *sizes, uint32_t root, double avg_record, hipStream_t stream);
 int launch_nested_index(NestedArgs a, double avg_record, hipStream_t stream);
 int launch_nested_decode(const spec_nested_schema *schema, NestedArgs a, double avg_record, hipStream_t stream);
 int launch_nested_onepass(const spec_nested_schema *schema, NestedArgs a, double avg_record, hipStream_t stream);
-// jit.cpp: nested decode specialised to the outer and item schemas (onepass: look-back kernel,
-// else the decode pass after the index kernels); 1 launched, 0 use the precompiled kernel,
-// <0 HIP error.  a.slab must be set.
-// mode: NESTED_ONEPASS (look-back kernel), NESTED_GROUPS (a wave per group after the index
-// kernels, items found by an owner search), NESTED_RANGES (same, items from ranges precomputed
-// into LDS by their records' lanes), NESTED_HALVES (as GROUPS, slabs for half a group),
-// NESTED_TAILCOUNT (as GROUPS, the count pass from each record's last 64 bytes), NESTED_XCD (as
-// TAILCOUNT with an XCD-aware block order for the decode pass: the default)
-// NESTED_PAIR_ONEPASS (round 6): the decode on wave pairs with one look-back per group, no
-// index kernels (spec_decode_nested_onepass)
-enum { NESTED_ONEPASS = 0, NESTED_GROUPS = 1, NESTED_RANGES = 2, NESTED_HALVES = 3, NESTED_TAILCOUNT = 4, NESTED_XCD = 5,
-       NESTED_PAIR_ONEPASS = 6 };
+// jit.cpp: the nested decode pass after the index kernels, specialised to the outer and item
+// schemas; 1 launched, 0 use the precompiled kernel, <0 HIP error.  a.slab must be set.
+// mode: NESTED_GROUPS (a wave pair per group, items found by an owner search) or NESTED_RANGES
+// (a wave per group, items from ranges precomputed into LDS by their records' lanes).  The other
+// values are spec_set_nested_mode's only (decode_nested.hip): NESTED_HALVES (as GROUPS, slabs for
+// half a group), NESTED_TAILCOUNT (as GROUPS, the count pass from each record's last 64 bytes),
+// NESTED_XCD (as TAILCOUNT with an XCD-aware block order for the decode pass: the default)
+enum { NESTED_GROUPS = 1, NESTED_RANGES = 2, NESTED_HALVES = 3, NESTED_TAILCOUNT = 4, NESTED_XCD = 5 };
 int jit_launch_nested(const spec_nested_schema *schema, const NestedArgs &a, int mode, hipStream_t stream);
-bool nested_lookback(); // build-time SPEC_AB_LOOKBACK: spec_decode_nested_onepass runs the look-back kernel
 long long jit_compile_only_nested(const spec_nested_schema *schema);
 // jit.cpp: schema-specialised decode kernel (hiprtc); returns 1 if launched, 0 if the caller
 // should launch the generic kernel, <0 on a HIP error.

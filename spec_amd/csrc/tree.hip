@@ -15,12 +15,6 @@
 
 namespace spec {
 
-// Build-time measurement switch (make HIPFLAGS+="-DSPEC_AB_TREE_ENC_SPLIT=1"): the encoder's
-// level-fused size / write launches split into one launch per table.
-#ifndef SPEC_AB_TREE_ENC_SPLIT
-#define SPEC_AB_TREE_ENC_SPLIT 0
-#endif
-
 unsigned row_grid(uint64_t rows) {
     const uint64_t b = (rows + TB - 1) / TB;
     const uint64_t cap = (uint64_t)device_cus() * 16;
@@ -659,7 +653,7 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
     // level-fused launches (tree_core.hpp TableSet) when the generated module has them: the
     // tables of one height sized together (children have smaller heights), the tables of one
     // depth written together (owners have smaller depths)
-    const bool sets = jit && jit[4 * TREE_MAX_T] && (jit[4 * TREE_MAX_T + 1] || jit[4 * TREE_MAX_T + 3]);
+    const bool sets = jit && jit[TREE_FN_SIZE_SET] && (jit[TREE_FN_WRITE_SET] || jit[TREE_FN_WRITE_TILE]);
     // the run-time writer keeps a message's field ends in LDS ([wave][field][lane], 256 B per field
     // per wave, 160 KiB per block at most): a table of more than 640 direct fields needs the
     // generated writer (jit.cpp).  Checked before anything is issued, so a call that cannot run
@@ -691,27 +685,12 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
                 most = std::max(most, rows[x]);
             }
         if (!ts.n) return true;
-#if SPEC_AB_TREE_ENC_SPLIT
-        // (measurement build: one launch per table, so a kernel trace times each table)
-        for (uint32_t j = 0; j < ts.n; j++) {
-            TableSet one;
-            one.n = 1;
-            one.t[0] = ts.t[j];
-            void *a1[] = {(void *)&Dd, (void *)&Bd, &one};
-            const hipError_t l1 = hipModuleLaunchKernel(fn, row_grid(rows[ts.t[j]]), 1, 1, TB, 1, 1, 0, st, a1, nullptr);
-            if (l1 != hipSuccess) {
-                note_hip_error(l1);
-                return false;
-            }
-        }
-        return true;
-#endif
         void *args[] = {(void *)&Dd, (void *)&Bd, &ts};
         const hipError_t le = hipModuleLaunchKernel(fn, row_grid(most), ts.n, 1, TB, 1, 1, 0, st, args, nullptr);
         if (le != hipSuccess) note_hip_error(le);
         return le == hipSuccess;
     };
-    for (int h = 0; sets && ok && h <= maxh; h++) ok = launch_set(jit[4 * TREE_MAX_T], height, h);
+    for (int h = 0; sets && ok && h <= maxh; h++) ok = launch_set(jit[TREE_FN_SIZE_SET], height, h);
     // (no generated module: the run-time row kernels) sizes bottom-up (children before their
     // owners: table order is pre-order)
     for (int x = (int)L.nt - 1; !sets && ok && x >= 0; x--)
@@ -741,17 +720,17 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
             hipLaunchKernelGGL(tree_pos_fill_kernel, dim3(gx, L.nt - 1), dim3(256), 0, st, pf);
         }
     }
-    const bool tile = sets && jit[4 * TREE_MAX_T + 3];
+    const bool tile = sets && jit[TREE_FN_WRITE_TILE];
     if (tile && ok && out && n) {
         uint32_t cap = TREE_TILE_IMG;
         void *args[] = {(void *)&Dd, (void *)&Bd, &cap};
-        const hipError_t le = hipModuleLaunchKernel(jit[4 * TREE_MAX_T + 3], (unsigned)((n + 63) / 64), 1, 1,
+        const hipError_t le = hipModuleLaunchKernel(jit[TREE_FN_WRITE_TILE], (unsigned)((n + 63) / 64), 1, 1,
                                                     64 * TREE_TILE_W, 1, 1, TREE_TILE_IMG + 16, st, args,
                                                     nullptr);
         if (le != hipSuccess) note_hip_error(le);
         ok = le == hipSuccess;
     }
-    for (int d = 0; sets && !tile && ok && out && d <= maxd; d++) ok = launch_set(jit[4 * TREE_MAX_T + 1], depth, d);
+    for (int d = 0; sets && !tile && ok && out && d <= maxd; d++) ok = launch_set(jit[TREE_FN_WRITE_SET], depth, d);
     bool too_wide = false;
     for (uint32_t x = 0; !sets && ok && out && !too_wide && x < L.nt; x++)
         if (rows[x]) {

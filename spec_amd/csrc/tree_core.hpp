@@ -586,9 +586,6 @@ struct GSink {
 };
 // (a tile's range may exceed the image: bytes past the image's window [sh, sh + cap) are stored
 // straight to the output — dwords are 4-byte aligned in both, so none straddles the window's end)
-#ifndef SPEC_TILE_OR
-#define SPEC_TILE_OR 0
-#endif
 typedef __attribute__((address_space(3))) uint8_t TileU8; // (writable: spec_device.hpp's lds_u8 is const)
 typedef __attribute__((address_space(3))) uint32_t TileU32;
 typedef __attribute__((address_space(3))) uint64_t TileU64;
@@ -609,7 +606,6 @@ struct LSink {
         else out[p] = (uint8_t)b;
     }
     __device__ __forceinline__ void word(uint64_t base, uint64_t from, uint64_t end, uint32_t v) const {
-#if SPEC_TILE_OR
         // the image starts zeroed and every byte belongs to one row: v's bytes outside [from, end)
         // are zero (a row's pending dword holds only its own bytes), so an OR merges the dword
         // with its neighbours' without the edge cases
@@ -617,7 +613,6 @@ struct LSink {
             __hip_atomic_fetch_or((TileU32 *)(img + at(base)), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             return;
         }
-#endif
         if (from == base && end == base + 4) {
             st32(base, v);
         } else {
@@ -1156,7 +1151,7 @@ struct MkL { // emitters over the LDS image of the window [sh, sh + cap), HBM pa
     __device__ __forceinline__ LEmit operator()(uint64_t p) const { return LEmit{{img, out, sh + cap, (uint32_t)sh}, p, p}; }
 };
 
-// zeroes the image's first `len` bytes (SPEC_TILE_OR: the rows OR their dwords into it)
+// zeroes the image's first `len` bytes (the rows OR their dwords into it, LSink::word)
 __device__ __forceinline__ void tile_clear(TileU8 *img, uint32_t len) {
     typedef unsigned int v4u __attribute__((ext_vector_type(4)));
     for (uint32_t a = threadIdx.x * 16u; a < len; a += blockDim.x * 16u) *(__attribute__((address_space(3))) v4u *)(img + a) = v4u{0, 0, 0, 0};

@@ -29,13 +29,9 @@
 namespace spec {
 namespace {
 
-// Build-time A/B (make HIPFLAGS+="-DSPEC_AB_TREE_PAIR=0"), never the environment: 0 runs the
-// root group's staged kernel one wave per 64 rows instead of two (gen_pair_rows; pkg1: 158 vs
-// 100 us).
-#ifndef SPEC_AB_TREE_PAIR
-#define SPEC_AB_TREE_PAIR 2
-#endif
-constexpr int tree_pair() { return SPEC_AB_TREE_PAIR == 2 ? 2 : 0; }
+// waves per 64 rows of the root group's staged kernel (jit.cpp gen_pair_rows; pkg1: 100 us
+// against 158 us on one wave)
+constexpr uint32_t TREE_PAIR = 2;
 
 // Group root x (the records or a list table) and the sub-message tables below it, a lane per
 // row, run-time schema.  LDS per wave: the staging slab, then a range slot per sub-message table
@@ -429,7 +425,7 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
             m.n++;
         }
     }
-    const hipFunction_t set_fn = d->jit && all_cols ? d->jit[4 * TREE_MAX_T + 2] : nullptr;
+    const hipFunction_t set_fn = d->jit && all_cols ? d->jit[TREE_FN_GROUP_SET] : nullptr;
     for (uint32_t level = 0; n && level <= maxlv; level++) {
         // the level's groups parsed from HBM by generated kernels: one level-fused launch when
         // there are two or more (pkg1's five list groups: 89.5 -> 70.5 us)
@@ -439,7 +435,7 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
         uint32_t fused_wb = 16;
         unsigned fused_grid = 1;
         for (uint32_t x = 1; set_fn && x < L.nt; x++) {
-            if (D.t[x].groot != x || lv[x] != level || d->caps[x] == 0 || !d->jit[x]) continue;
+            if (D.t[x].groot != x || lv[x] != level || d->caps[x] == 0 || !d->jit[TREE_FN_GROUP + x]) continue;
             const GroupShape gs = group_shape(L, x, stream_len, d->caps[x]);
             if (gs.slab) continue;
             fused.t[fused.n++] = x;
@@ -467,12 +463,12 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
             const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((cap + per_block - 1) / per_block, 1u << 20));
             const size_t lds = (size_t)wpb * gs.wave_bytes;
             const hipFunction_t pair_fn =
-                tree_pair() && d->jit && all_cols && gs.slab ? d->jit[2 * TREE_MAX_T + x] : nullptr;
+                d->jit && all_cols && gs.slab ? d->jit[TREE_FN_GROUP_PAIR + x] : nullptr;
             if (pair_fn) {
                 // the root group on P waves per 64 rows: one slab, the waves decoding it
                 // (tree_rows_pair), one set of range slots, a 1 KiB exchange per extra wave (pkg1:
                 // 35 KiB slab + 2 KiB slots + 1-3 KiB = four blocks per CU)
-                const uint32_t gn = D.t[x].gn, P = (uint32_t)tree_pair();
+                const uint32_t gn = D.t[x].gn, P = TREE_PAIR;
                 uint32_t xx = x, slab = gs.slab, slots = 512u * (gn > 1 ? gn - 1 : 0), rpw = 64;
                 void *args[] = {(void *)&Dd, (void *)&Bd, &xx, &slab, &slots, &rpw};
                 const unsigned grid = (unsigned)std::min<uint64_t>((cap + 63) / 64, 1u << 20);
@@ -482,11 +478,12 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
                     note_hip_error(le);
                     return SPEC_E_HIP;
                 }
-            } else if (d->jit && d->jit[x] && all_cols) {
+            } else if (d->jit && d->jit[TREE_FN_GROUP + x] && all_cols) {
                 uint32_t xx = x, slab = gs.slab, wb = gs.wave_bytes, rpw = gs.rpw;
                 void *args[] = {(void *)&Dd, (void *)&Bd, &xx, &slab, &wb, &rpw};
                 // rows from HBM: the kernel without staging code (fewer registers, more waves)
-                const hipFunction_t fn = gs.slab == 0 && d->jit[TREE_MAX_T + x] ? d->jit[TREE_MAX_T + x] : d->jit[x];
+                const hipFunction_t hbm = d->jit[TREE_FN_GROUP_HBM + x];
+                const hipFunction_t fn = gs.slab == 0 && hbm ? hbm : d->jit[TREE_FN_GROUP + x];
                 const unsigned grid = gs.slab == 0 ? row_grid(cap) : (unsigned)blocks;
                 const hipError_t le =
                     hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, (unsigned)lds, st, args, nullptr);

@@ -23,6 +23,19 @@ struct Layout {
     TreeDesc desc;
 };
 
+// jit.cpp jit_tree_kernels(): the kernels of a tree's generated module by these indices, nullptr
+// where the module has none and the run-time kernel runs.
+enum TreeFn {
+    TREE_FN_GROUP = 0,                   // + x: decode of group root x, rows staged in LDS
+    TREE_FN_GROUP_HBM = TREE_MAX_T,      // + x: the same, rows from HBM (no staging code)
+    TREE_FN_GROUP_PAIR = 2 * TREE_MAX_T, // + x: on 2 waves per 64 rows (root group only, if it splits)
+    TREE_FN_SIZE_SET = 3 * TREE_MAX_T,   // the encoder's level-fused size pass
+    TREE_FN_WRITE_SET,                   // its level-fused writer, or
+    TREE_FN_WRITE_TILE,                  // its record-tile writer (one of the two is generated)
+    TREE_FN_GROUP_SET,                   // the level-fused list-group decode
+    TREE_FN_COUNT
+};
+
 // Builds the layout; false on an invalid tree (rules: include/spec_amd.h spec_tree).
 bool build_layout(const spec_tree *tr, Layout &L);
 

@@ -266,13 +266,13 @@ __global__ __launch_bounds__(DEEP_THREADS) void deep_kernel(DecodeArgs a, uint32
 
 int launch_parse(DecodeArgs a, uint32_t *sizes, uint32_t root, double avg_record, hipStream_t stream) {
     if (a.n <= a.r0) return 0;
-    const DecodeLaunch L = decode_launch(a.n - a.r0, avg_record, device_cus(), false, 1);
+    const DecodeLaunch L = decode_launch(a.n - a.r0, avg_record);
     a.slab = L.slab;
     // the deep pass's list and arena: stream-ordered scratch of this call
     DeepWs *deep = nullptr;
     if (hipMallocAsync((void **)&deep, DEEP_WS_BYTES, stream) != hipSuccess) return -1;
     if (hipMemsetAsync(deep, 0, sizeof(uint32_t), stream) != hipSuccess) return -1;
-    hipLaunchKernelGGL(parse_kernel, dim3(L.blocks), dim3(64 * L.wpb), L.lds, stream, a, sizes, root, deep);
+    hipLaunchKernelGGL(parse_kernel, dim3(L.blocks), dim3(64), L.slab, stream, a, sizes, root, deep);
     hipLaunchKernelGGL(deep_kernel, dim3(1), dim3(DEEP_THREADS), 0, stream, a, sizes, root, deep);
     if (hipFreeAsync(deep, stream) != hipSuccess) return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -360,8 +360,8 @@ def test_encode_schemas(dev, kernel, case):
 def test_encode_pair_groups_over_slab(dev, kernel, n):
     """64-record groups whose bytes exceed the write pass's slab (long strings: written straight
     to HBM) among groups staged in LDS, single long records inside staged groups, a partial last
-    block and group — the bytes stay the oracle Writer's.  (It was written for the wave-pair write
-    pass, encode_write_pair_body, built with -DSPEC_AB_ENC_PAIR=1, and passed there too.)"""
+    block and group — the bytes stay the oracle Writer's.  (It was written for a wave-pair write
+    pass of the flat encoder, which was measured no faster and removed, and passed there too.)"""
     a_cols, a_heaps = workload.flat16(n, seed=21)
     b_cols, b_heaps = workload.gen_columns(FLAT16, n, 22, str_len=(300, 700))
     big = np.zeros(n, bool)

@@ -1,8 +1,9 @@
 #!/bin/bash
-# Build an A/B variant of the engine: spec_amd/libspec_amd_NAME.so with extra -D flags (objects
-# under spec_amd/csrc/build/v_NAME, which gpurun does not upload), then precompile its Flat16 /
-# Nested schema-specialised kernels into the shared jit_cache.
-# Usage: bash tools/build_variant.sh NAME "-DSPEC_AB_X=0 ..."
+# Build a side library for an experiment: spec_amd/libspec_amd_NAME.so with extra compiler flags
+# (objects under spec_amd/csrc/build/v_NAME), then load it and precompile its Flat16 / Nested /
+# pkg1-tree schema-specialised kernels into the shared jit_cache.  The runners that take variant
+# names (tools/gpu_headline_ab.sh, gpu_wide_ab.sh, gpu_nenc_ab.sh, gpu_tree_ab.sh) swap it in.
+# Usage: bash tools/build_variant.sh NAME "-DMY_EXPERIMENT=1 ..."
 set -e
 NAME=$1; FLAGS=$2
 cd "$(dirname "$0")/.."
@@ -18,5 +19,6 @@ L.spec_decode_flat_jit_compile(C.byref(spec_amd.FLAT16.c), 1 << 28, 1 << 20)
 L.spec_encode_flat_jit_compile(C.byref(spec_amd.FLAT16.c))
 L.spec_decode_nested_jit_compile(C.byref(spec_amd.NESTED.c))
 L.spec_encode_nested_jit_compile(C.byref(spec_amd.NESTED.c))
+print(L.spec_tree_jit_compile(C.byref(spec_amd.pkg1_tree().c)))
 PY
 echo built spec_amd/libspec_amd_$NAME.so

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Tree encode A/B: tools/bench_tree.py alternating the default library and each variant
-# (spec_amd/libspec_amd_<v>.so, tools/build_tree_variant.sh), 3 runs each.
+# (spec_amd/libspec_amd_<v>.so, tools/build_variant.sh), 3 runs each.
 # Usage (GPU box): bash tools/gpu_tree_ab.sh TAG [variant ...]
 set -o pipefail
 TAG=${1:-treeab}; shift
