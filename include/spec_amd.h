@@ -268,6 +268,18 @@ long long spec_tree_jit_compile(const spec_tree *tree);
  * is a Go panic (STATUS SPEC_STATUS_PANIC).  Decode with spec_tree_decoder_decode as usual. */
 int spec_tree_decoder_index_spans(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len,
                                   const spec_span *spans, uint64_t n, uint64_t *rows, void *stream);
+/* spec_tree_decoder_index / spec_tree_decoder_run over mpx FRAMES in place (mpx/conn_reader.go:179-194:
+ * [u32 big-endian size][message], back to back): ends are the frame ends spec_frames_index[_device]
+ * reports, so row i of the root table is frames[ends[i-1] + 4, ends[i]) — no span array, no copy.
+ * A frame whose ends are not 4 apart (ends[i] < ends[i-1] + 4) is an empty message.  String, bytes
+ * and any spans are offsets into frames.  spec_tree_decoder_decode after
+ * spec_tree_decoder_index_frames decodes the frames; the head holds for that batch only.
+ * Arguments, return codes and limits otherwise as spec_tree_decoder_index / spec_tree_decoder_run. */
+int spec_tree_decoder_index_frames(spec_tree_decoder *d, const uint8_t *frames, uint64_t frames_len,
+                                   const uint64_t *ends, uint64_t n, uint64_t *rows, void *stream);
+int spec_tree_decoder_run_frames(spec_tree_decoder *d, const uint8_t *frames, uint64_t frames_len,
+                                 const uint64_t *ends, uint64_t n, void *const *columns, const uint64_t *col_rows,
+                                 uint64_t *rows_out, void *stream);
 
 /* Value.<Kind>() / Value.<Kind>Err() (internal/types/value.go:120-310) over n value spans (an
  * `any` column): out[i] = Decode<Kind>(the span's bytes) (n * spec_kind_width(kind) bytes;
@@ -471,6 +483,12 @@ int spec_frames_index(const uint8_t *buf, uint64_t len, uint64_t *ends, uint64_t
 int spec_decode_frames(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
                        const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes, void *const *columns,
                        uint8_t *status, void *stream);
+/* spec_decode_frames_errors: spec_decode_frames with the per-record field error masks of
+ * spec_decode_flat_errors (errmask[r], bit f = field f's <Kind>Err getter errs; a schema of more
+ * than 64 fields: word c of record r at errmask[c * r1 + r]).  errmask must not be NULL. */
+int spec_decode_frames_errors(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                              const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes,
+                              void *const *columns, uint8_t *status, uint64_t *errmask, void *stream);
 /* spec_frames_index_device: spec_frames_index on a DEVICE buffer (4-byte aligned), with the same
  * results: ends[0, min(frames, cap)), *count, *consumed (device uint64) and *status (device int32:
  * SPEC_OK, or SPEC_E_CAPACITY when more than cap complete frames exist — then *count = cap).  The
@@ -599,6 +617,13 @@ int spec_host_decoder_chunk(const spec_host_decoder *d, uint64_t n, uint32_t k, 
                             uint64_t *col_offsets, uint64_t *status_offset);
 int spec_host_decoder_run(spec_host_decoder *d, const uint8_t *stream_host, uint64_t stream_len,
                           const uint64_t *ends_host, uint64_t n, uint8_t *out_host);
+/* spec_host_decoder_run over the frames as the receive loop of mpx/conn_reader.go:179-194 holds
+ * them: frames_host = [u32 BE size][message] back to back, ends_host = the frame ends
+ * (spec_frames_index).  Chunk k copies the bytes [ends[r0-1], ends[r1-1]) — its frames, heads
+ * included — and decodes them with spec_decode_frames; spans are offsets into frames_host.
+ * stream_cap bounds frames_len.  Outputs and return codes as spec_host_decoder_run. */
+int spec_host_decoder_run_frames(spec_host_decoder *d, const uint8_t *frames_host, uint64_t frames_len,
+                                 const uint64_t *ends_host, uint64_t n, uint8_t *out_host);
 
 /* The host pipeline on every device of a spec_shard at once (host batch in, host columns out,
  * one host thread per device): spec_shard_host_prepare creates a spec_host_decoder per device
@@ -695,6 +720,23 @@ int spec_decode_nested_onepass(const spec_nested_schema *schema, const uint8_t *
                                uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
                                uint64_t item_cap, void *workspace, size_t workspace_size, uint64_t *total_items,
                                void *stream);
+/* The three calls above over mpx FRAMES in place (mpx/conn_reader.go:179-194: [u32 big-endian
+ * size][message], back to back): ends are the frame ends spec_frames_index[_device] reports, so
+ * record i is frames[ends[i-1] + 4, ends[i]); a frame with ends[i] < ends[i-1] + 4 is an empty
+ * record.  String and bytes spans are offsets into frames.  Arguments, return codes, workspace
+ * and the < 4 GiB limit (on frames_len) as their unframed twins. */
+int spec_decode_nested_frames_index(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                                    const uint64_t *ends, uint64_t n, void *workspace, size_t workspace_size,
+                                    uint64_t *total_items, void *stream);
+int spec_decode_nested_frames(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                              const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                              uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                              uint64_t item_cap, void *workspace, size_t workspace_size, void *stream);
+int spec_decode_nested_frames_onepass(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                                      const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                                      uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                                      uint64_t item_cap, void *workspace, size_t workspace_size,
+                                      uint64_t *total_items, void *stream);
 /* spec_set_nested_mode: the kernels of spec_decode_nested_index / spec_decode_nested (results
  * never differ; times per 1M config-4 records, index + decode):
  * 5 (default) as 4, the decode pass's blocks in XCD-aware order (neighbouring groups, which share

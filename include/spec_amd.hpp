@@ -8,6 +8,8 @@
 //   spec::MessageBatchWriter    ~ spec.NewMessageWriterBuffer + w.Field(tag).<Kind>(v) + w.Build()
 //                                 (writer_msg.go:26-31, internal/writer/msg.go:56-60, 99-211)
 //   spec::ParseMessageBatch     ~ spec.ParseMessage (msg.go:29-32)
+//   spec::OpenMessageFrames     ~ OpenMessageBatch over the frames an mpx connection carries, in
+//                                 place (mpx/conn_reader.go:179-194)
 // Errors: a failed call throws spec::Error carrying the spec_rc and its text; per-record
 // errors are the status column (the error class OpenMessageErr/ParseMessage would return).
 // Buffers are RAII wrappers of spec_device_alloc / spec_host_alloc; nothing here touches a
@@ -138,6 +140,8 @@ struct Batch {
     uint64_t len = 0, n = 0;
 };
 
+struct Frames;
+
 // Decoded columns of a batch (one per schema field) + the per-record status.
 class MessageBatch {
   public:
@@ -149,6 +153,7 @@ class MessageBatch {
 
   private:
     friend MessageBatch OpenMessageBatch(const Schema &, const Batch &, Stream &);
+    friend MessageBatch OpenMessageFrames(const Schema &, const Frames &, Stream &);
     std::vector<DeviceBuffer> cols_;
     DeviceBuffer status_;
     uint64_t n_ = 0;
@@ -186,6 +191,25 @@ struct Frames {
     DeviceBuffer bytes, ends;
     uint64_t len = 0, n = 0;
 };
+
+// OpenMessageBatch over frames where they lie (connReader.readMessage's frames, conn_reader.go:179-194:
+// record i = bytes[ends[i-1] + 4, ends[i])): no unframed copy.  String and bytes spans are offsets
+// into f.bytes.
+inline MessageBatch OpenMessageFrames(const Schema &schema, const Frames &f, Stream &s) {
+    MessageBatch m;
+    m.n_ = f.n;
+    std::vector<void *> ptrs;
+    for (size_t k = 0; k < schema.Len(); k++) {
+        m.cols_.emplace_back((size_t)f.n * Width(schema.KindOf(k)) + 1);
+        ptrs.push_back(m.cols_.back().data());
+    }
+    m.status_ = DeviceBuffer(f.n + 1);
+    spec_schema c = schema.C();
+    Check(spec_decode_frames(&c, (const uint8_t *)f.bytes.data(), f.len, (const uint64_t *)f.ends.data(), 0, f.n, 0,
+                             ptrs.data(), (uint8_t *)m.status_.data(), s.get()),
+          "spec_decode_frames");
+    return m;
+}
 
 // For every record: w := NewMessageWriterBuffer(buf); w.Field(tag_f).<Kind_f>(column_f[i])...; w.Build().
 class MessageBatchWriter {
@@ -381,6 +405,16 @@ class HostMessageReader {
         if (out.size() < OutBytes(n) || ends.size() < n * 8) throw Error(SPEC_E_CAPACITY, "HostMessageReader::Read");
         Check(spec_host_decoder_run(d_, stream.data(), stream_len, (const uint64_t *)ends.data(), n, out.data()),
               "spec_host_decoder_run");
+    }
+    // Read over the frames as the connection's buffer holds them: frames = [u32 BE size][message]
+    // back to back, ends = the frame ends (spec_frames_index); spans are offsets into frames.
+    void ReadFrames(const PinnedBuffer &frames, uint64_t frames_len, const PinnedBuffer &ends, uint64_t n,
+                    PinnedBuffer &out) {
+        if (out.size() < OutBytes(n) || ends.size() < n * 8)
+            throw Error(SPEC_E_CAPACITY, "HostMessageReader::ReadFrames");
+        Check(spec_host_decoder_run_frames(d_, frames.data(), frames_len, (const uint64_t *)ends.data(), n,
+                                           out.data()),
+              "spec_host_decoder_run_frames");
     }
     struct ChunkView {
         uint64_t r0, r1;

@@ -10,13 +10,14 @@ from .batch import (PARSE_LIST, PARSE_MESSAGE, PARSE_VALUE, Columns, Decoder, En
                     decode_flat_errors, encode_flat, encode_flat_frames, parse_messages)
 from . import lz4
 from .lz4 import Lz4Writer, compress_frame, frame_bound
-from .frames import decode_frames, frames_index, frames_index_device, make_frames, make_frames_device, write_frames
+from .frames import (decode_frames, decode_frames_errors, frames_index, frames_index_device, make_frames, make_frames_device,
+                     write_frames)
 from .pipeline import HostDecoder
-from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, encode_nested,
-                     encode_nested_frames)
+from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, decode_nested_frames,
+                     encode_nested, encode_nested_frames)
 from .schema import FLAT16, NESTED, Field, Kind, NestedSchema, Schema
-from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, TreeEncoder, decode_tree, decode_values,
-                   encode_tree, encode_tree_frames, pkg1_message, pkg1_tree, tree_rows)
+from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, TreeEncoder, decode_tree, decode_tree_frames,
+                   decode_values, encode_tree, encode_tree_frames, pkg1_message, pkg1_tree, tree_rows)
 
 __all__ = [
     "HostDecoder", "decode_frames", "frames_index", "frames_index_device", "make_frames", "make_frames_device", "write_frames", "Lz4Writer", "compress_frame", "frame_bound", "LIB_PATH", "SpecError", "header_symbols", "lib", "set_jit", "Columns", "Decoder", "Encoder", "alloc_columns",
@@ -25,4 +26,5 @@ __all__ = [
     "NESTED", "NestedSchema", "NestedColumns", "NestedDecoder", "NestedEncoder", "decode_nested",
     "encode_nested", "encode_nested_frames", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
     "decode_values", "encode_tree", "encode_tree_frames", "pkg1_message", "pkg1_tree", "tree_rows",
+    "decode_frames_errors", "decode_nested_frames", "decode_tree_frames",
 ]

@@ -254,6 +254,15 @@ def _declare(L):
     L.spec_encode_tree.argtypes = [C.POINTER(SpecTree), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64),
                                    C.POINTER(C.c_uint64), vp, C.c_uint64, vp, vp, C.c_size_t, vp, vp]
     L.spec_encode_tree_frames.argtypes = L.spec_encode_tree.argtypes
+    # the decoders over mpx frames: their unframed twins' arguments (ends = frame ends)
+    L.spec_decode_frames_errors.argtypes = [C.POINTER(SpecSchema), vp, C.c_uint64, vp, C.c_uint64, C.c_uint64,
+                                            C.c_uint64, C.POINTER(vp), vp, vp, vp]
+    L.spec_decode_nested_frames_index.argtypes = L.spec_decode_nested_index.argtypes
+    L.spec_decode_nested_frames.argtypes = L.spec_decode_nested.argtypes
+    L.spec_decode_nested_frames_onepass.argtypes = L.spec_decode_nested_onepass.argtypes
+    L.spec_tree_decoder_index_frames.argtypes = L.spec_tree_decoder_index.argtypes
+    L.spec_tree_decoder_run_frames.argtypes = L.spec_tree_decoder_run.argtypes
+    L.spec_host_decoder_run_frames.argtypes = L.spec_host_decoder_run.argtypes
 
 
 def strerror(rc: int) -> str:

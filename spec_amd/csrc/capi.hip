@@ -471,6 +471,15 @@ int spec_decode_frames(const spec_schema *schema, const uint8_t *frames, uint64_
     return decode_flat_impl(schema, frames, frames_len, ends, r0, r1, range_bytes, 4, columns, status, stream);
 }
 
+// spec_decode_frames with the per-record field error masks of spec_decode_flat_errors
+int spec_decode_frames_errors(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                              const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes,
+                              void *const *columns, uint8_t *status, uint64_t *errmask, void *stream) {
+    if (!errmask && r1 > r0) return SPEC_E_INVALID_ARGUMENT;
+    return decode_flat_impl(schema, frames, frames_len, ends, r0, r1, range_bytes, 4, columns, status, stream,
+                            errmask);
+}
+
 // mpx framing, mpx/conn_reader.go:179-194 (read) / mpx/conn_writer.go:84-97 (write):
 // [u32 big-endian size][size message bytes], back to back.
 int spec_frames_index(const uint8_t *buf, uint64_t len, uint64_t *ends, uint64_t cap, uint64_t *count,
@@ -568,9 +577,11 @@ long long spec_encode_flat_jit_compile(const spec_schema *schema) {
 
 size_t spec_decode_nested_workspace_size(uint64_t n) { return (size_t)(((n + 63) / 64 + 1) * sizeof(uint64_t)); }
 
+// head: bytes before each record (0, or 4 when ends are mpx frame ends); this one builder serves the
+// index, the decode, the one-pass call and the chunked wide-half route
 static int nested_args(spec::NestedArgs &a, const spec_nested_schema *schema, const uint8_t *stream_bytes,
                        uint64_t stream_len, const uint64_t *ends, uint64_t n, void *workspace,
-                       size_t workspace_size) {
+                       size_t workspace_size, uint32_t head) {
     uint32_t list_f = 0;
     int rc = check_nested(schema, &list_f);
     if (rc) return rc;
@@ -582,6 +593,7 @@ static int nested_args(spec::NestedArgs &a, const spec_nested_schema *schema, co
     a.stream_len = stream_len;
     a.ends = ends;
     a.n = n;
+    a.head = head;
     fill_field_set(a.outer, &schema->outer, nullptr, nullptr, 0, SPEC_KFIELDS);
     fill_field_set(a.item, &schema->item, nullptr, nullptr, 0, SPEC_KFIELDS);
     a.list_tag = schema->outer.fields[list_f].tag;
@@ -617,11 +629,11 @@ static int nested_decode_chunks(const spec_nested_schema *schema, spec::NestedAr
     return SPEC_OK;
 }
 
-int spec_decode_nested_index(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+static int nested_index_impl(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
                              const uint64_t *ends, uint64_t n, void *workspace, size_t workspace_size,
-                             uint64_t *total_items, void *stream) {
+                             uint64_t *total_items, void *stream, uint32_t head) {
     spec::NestedArgs a{};
-    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size);
+    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size, head);
     if (rc) return rc;
     if (!total_items) return SPEC_E_INVALID_ARGUMENT;
     a.total = total_items;
@@ -630,12 +642,13 @@ int spec_decode_nested_index(const spec_nested_schema *schema, const uint8_t *st
     return SPEC_OK;
 }
 
-int spec_decode_nested(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
-                       const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
-                       uint32_t *item_begin, void *const *item_columns, uint8_t *item_status, uint64_t item_cap,
-                       void *workspace, size_t workspace_size, void *stream) {
+static int nested_decode_impl(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                              const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                              uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                              uint64_t item_cap, void *workspace, size_t workspace_size, void *stream,
+                              uint32_t head) {
     spec::NestedArgs a{};
-    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size);
+    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size, head);
     if (rc) return rc;
     if (n == 0) return SPEC_OK;
     if (!outer_columns || !item_begin || (item_cap && !item_columns)) return SPEC_E_INVALID_ARGUMENT;
@@ -649,13 +662,13 @@ int spec_decode_nested(const spec_nested_schema *schema, const uint8_t *stream_b
     return nested_decode_chunks(schema, a, outer_columns, status, item_columns, item_status, avg, (hipStream_t)stream);
 }
 
-int spec_decode_nested_onepass(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+static int nested_onepass_impl(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
                                const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
                                uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
                                uint64_t item_cap, void *workspace, size_t workspace_size, uint64_t *total_items,
-                               void *stream) {
+                               void *stream, uint32_t head) {
     spec::NestedArgs a{};
-    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size);
+    int rc = nested_args(a, schema, stream_bytes, stream_len, ends, n, workspace, workspace_size, head);
     if (rc) return rc;
     if (!total_items) return SPEC_E_INVALID_ARGUMENT;
     a.total = total_items;
@@ -688,6 +701,57 @@ int spec_decode_nested_onepass(const spec_nested_schema *schema, const uint8_t *
     a.item.status = item_cap ? item_status : nullptr;
     if (spec::launch_nested_onepass(schema, a, avg, (hipStream_t)stream)) return hip_rc(hipGetLastError());
     return SPEC_OK;
+}
+
+int spec_decode_nested_index(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                             const uint64_t *ends, uint64_t n, void *workspace, size_t workspace_size,
+                             uint64_t *total_items, void *stream) {
+    return nested_index_impl(schema, stream_bytes, stream_len, ends, n, workspace, workspace_size, total_items, stream,
+                             0);
+}
+
+int spec_decode_nested(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                       const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                       uint32_t *item_begin, void *const *item_columns, uint8_t *item_status, uint64_t item_cap,
+                       void *workspace, size_t workspace_size, void *stream) {
+    return nested_decode_impl(schema, stream_bytes, stream_len, ends, n, outer_columns, status, item_begin,
+                              item_columns, item_status, item_cap, workspace, workspace_size, stream, 0);
+}
+
+int spec_decode_nested_onepass(const spec_nested_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                               const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                               uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                               uint64_t item_cap, void *workspace, size_t workspace_size, uint64_t *total_items,
+                               void *stream) {
+    return nested_onepass_impl(schema, stream_bytes, stream_len, ends, n, outer_columns, status, item_begin,
+                               item_columns, item_status, item_cap, workspace, workspace_size, total_items, stream, 0);
+}
+
+// The nested decoders over mpx frames (mpx/conn_reader.go:179-194: [u32 BE size][message], back to
+// back): ends are the FRAME ends spec_frames_index[_device] reports, so record i is
+// frames[ends[i-1] + 4, ends[i]).  The same kernels with NestedArgs::head = 4; the slabs are sized
+// from frames_len / n (the heads are part of the staged span); spans are offsets into frames.
+int spec_decode_nested_frames_index(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                                    const uint64_t *ends, uint64_t n, void *workspace, size_t workspace_size,
+                                    uint64_t *total_items, void *stream) {
+    return nested_index_impl(schema, frames, frames_len, ends, n, workspace, workspace_size, total_items, stream, 4);
+}
+
+int spec_decode_nested_frames(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                              const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                              uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                              uint64_t item_cap, void *workspace, size_t workspace_size, void *stream) {
+    return nested_decode_impl(schema, frames, frames_len, ends, n, outer_columns, status, item_begin, item_columns,
+                              item_status, item_cap, workspace, workspace_size, stream, 4);
+}
+
+int spec_decode_nested_frames_onepass(const spec_nested_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                                      const uint64_t *ends, uint64_t n, void *const *outer_columns, uint8_t *status,
+                                      uint32_t *item_begin, void *const *item_columns, uint8_t *item_status,
+                                      uint64_t item_cap, void *workspace, size_t workspace_size,
+                                      uint64_t *total_items, void *stream) {
+    return nested_onepass_impl(schema, frames, frames_len, ends, n, outer_columns, status, item_begin, item_columns,
+                               item_status, item_cap, workspace, workspace_size, total_items, stream, 4);
 }
 
 long long spec_decode_nested_jit_compile(const spec_nested_schema *schema) {

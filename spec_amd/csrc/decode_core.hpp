@@ -72,6 +72,7 @@ struct NestedArgs {
     uint64_t *total;      // device: total items
     uint32_t slab;        // LDS bytes per wave
     uint32_t xcd;         // decode pass: 1 = XCD-aware block order (grid a multiple of 8)
+    uint32_t head;        // bytes before each record (DecodeArgs::head; 4: ends are mpx frame ends)
 };
 
 constexpr int DEC_WAVES = 4; // waves per block of the nested kernels

@@ -100,7 +100,7 @@ __device__ __forceinline__ Group nested_stage_part(const NestedArgs &a, __amdgpu
     d.ends = a.ends;
     d.n = a.n;
     d.r0 = 0;
-    d.head = 0;
+    d.head = a.head;
     load_group_ends(d, base, lane, lo, hi);
     Group gr = make_group(a.n, base, lo, hi, a.slab, l0, l1);
     if (gr.in_lds) stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
@@ -411,7 +411,7 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     d.ends = a.ends;
     d.n = a.n;
     d.r0 = 0;
-    d.head = 0;
+    d.head = a.head;
     uint64_t lo, hi;
     load_group_ends(d, base, lane, lo, hi);
     const Group gr = make_group(d, base, lane, lo, hi, a.slab);
@@ -562,7 +562,7 @@ __device__ __forceinline__ void nested_count_tail_body(const NestedArgs &a, uint
     DecodeArgs d;
     d.ends = a.ends;
     d.n = a.n;
-    d.head = 0;
+    d.head = a.head;
     uint64_t lo, hi;
     load_group_ends(d, base, lane, lo, hi);
     if (hi < lo) hi = lo; // malformed ends: an empty record (make_group)

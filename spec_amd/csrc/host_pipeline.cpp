@@ -62,6 +62,11 @@ int hip_fail(hipError_t e) {
     return SPEC_E_HIP;
 }
 
+// host_decoder_run_based with `head` bytes before every record: 0, or 4 for a batch of mpx frames
+// (ends = frame ends; a chunk's byte range [ends[r0-1], ends[r1-1]) then holds its frames' heads too)
+int run_based(spec_host_decoder *d, const uint8_t *stream_host, uint64_t stream_len, const uint64_t *ends_host,
+              uint64_t n, uint64_t ends_base, uint32_t head, uint8_t *out_host);
+
 } // namespace
 
 namespace spec {
@@ -165,10 +170,22 @@ int spec_host_decoder_run(spec_host_decoder *d, const uint8_t *stream_host, uint
     return spec::host_decoder_run_based(d, stream_host, stream_len, ends_host, n, 0, out_host);
 }
 
+// spec_host_decoder_run over mpx frames as a receiver holds them (mpx/conn_reader.go:179-194)
+int spec_host_decoder_run_frames(spec_host_decoder *d, const uint8_t *frames_host, uint64_t frames_len,
+                                 const uint64_t *ends_host, uint64_t n, uint8_t *out_host) {
+    return run_based(d, frames_host, frames_len, ends_host, n, 0, 4, out_host);
+}
+
 } // extern "C"
 
 int spec::host_decoder_run_based(spec_host_decoder *d, const uint8_t *stream_host, uint64_t stream_len,
                                  const uint64_t *ends_host, uint64_t n, uint64_t ends_base, uint8_t *out_host) {
+    return run_based(d, stream_host, stream_len, ends_host, n, ends_base, 0, out_host);
+}
+
+namespace {
+int run_based(spec_host_decoder *d, const uint8_t *stream_host, uint64_t stream_len, const uint64_t *ends_host,
+              uint64_t n, uint64_t ends_base, uint32_t head, uint8_t *out_host) {
     if (!d || n > d->n_cap || stream_len > d->stream_cap) return SPEC_E_INVALID_ARGUMENT;
     if (n == 0) return SPEC_OK;
     if (!stream_host || !ends_host || !out_host) return SPEC_E_INVALID_ARGUMENT;
@@ -209,8 +226,10 @@ int spec::host_decoder_run_based(spec_host_decoder *d, const uint8_t *stream_hos
             // column f of this chunk, shifted by -r0 rows (the kernel indexes by record)
             for (uint32_t f = 0; f < d->schema.nfields; f++)
                 cols[f] = d->d_out + col_off[f] - r0 * (uint64_t)spec_kind_width(d->schema.fields[f].kind);
-            rc = spec_decode_flat_range(&d->schema, d->d_stream, stream_len, d->d_ends, r0, r1, b1 - b0, cols,
-                                        d->d_out + status_off - r0, d->s_dec);
+            rc = head ? spec_decode_frames(&d->schema, d->d_stream, stream_len, d->d_ends, r0, r1, b1 - b0, cols,
+                                           d->d_out + status_off - r0, d->s_dec)
+                      : spec_decode_flat_range(&d->schema, d->d_stream, stream_len, d->d_ends, r0, r1, b1 - b0, cols,
+                                               d->d_out + status_off - r0, d->s_dec);
             if (rc != SPEC_OK) break;
             if ((e = hipEventRecord(d->ev_dec[k], d->s_dec)) != hipSuccess ||
                 (e = hipStreamWaitEvent(d->s_out, d->ev_dec[k], 0)) != hipSuccess ||
@@ -229,3 +248,4 @@ int spec::host_decoder_run_based(spec_host_decoder *d, const uint8_t *stream_hos
     if (prev != d->device) (void)hipSetDevice(prev);
     return rc;
 }
+} // namespace

@@ -100,6 +100,9 @@ struct TreeBufs {
     // absolute positions and only the root writers know the head: the u32 big-endian size[0][row]
     // at start - 4, the first append of the record's own emitter
     uint32_t frame_head;
+    // decode: bytes before each record of table 0 (row_range; 4: ends are mpx frame ends, every
+    // record behind its [u32 BE size] head).  Set by every run(); spans ignore it
+    uint32_t head;
 };
 
 __device__ __forceinline__ uint64_t grid_stride() { return (uint64_t)gridDim.x * blockDim.x; }
@@ -124,7 +127,7 @@ __device__ __forceinline__ void row_range(const TreeBufs &B, uint32_t x, uint64_
             hi = out ? 0 : (long long)sp.x + sp.y;
             return;
         }
-        lo = row ? (long long)B.ends[row - 1] : 0;
+        lo = (row ? (long long)B.ends[row - 1] : 0) + (long long)B.head;
         hi = (long long)B.ends[row];
         if (hi < lo) hi = lo;
         return;

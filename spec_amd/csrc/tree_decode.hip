@@ -357,8 +357,11 @@ int upload(spec_tree_decoder *d, hipStream_t st) {
 // col_rows (optional, host, per table): rows the caller's columns hold; every group's rows are
 // clamped to them (its tables' columns, and the BEGIN columns of the lists it owns: owner rows +
 // 1 entries), so nothing is written past a column; a clamped list reports ~0 in rows_out.
+// head: bytes before each record (0, or 4 when ends are mpx frame ends; spans ignore it).  Set by
+// every call, so it never carries over from one batch to the next.
 int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends,
-        const uint2 *spans, uint64_t n, void *const *columns, const uint64_t *col_rows, hipStream_t st) {
+        const uint2 *spans, uint32_t head, uint64_t n, void *const *columns, const uint64_t *col_rows,
+        hipStream_t st) {
     if (stream_len >= (1ull << 32)) return SPEC_E_TOO_LARGE;
     if (n && (!stream_bytes || (!ends && !spans))) return SPEC_E_INVALID_ARGUMENT;
     Layout &L = d->L;
@@ -382,6 +385,7 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
     B.stream_len = stream_len;
     B.ends = ends;
     B.spans = spans;
+    B.head = spans ? 0 : head;
     B.n = n;
     B.rowsd = (uint64_t *)d->misc.p;
     bool all_cols = columns != nullptr; // the schema-specialised kernels store every column unconditionally
@@ -519,12 +523,12 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
 // index: a decode without columns, then the row counts on the host; list capacities grow and
 // the pass reruns when a list outgrew them (at most once per growth).
 int index(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends,
-          const uint2 *spans, uint64_t n, uint64_t *rows, hipStream_t st) {
+          const uint2 *spans, uint32_t head, uint64_t n, uint64_t *rows, hipStream_t st) {
     Layout &L = d->L;
     // an inner list's count is exact only once its owner list fits: at most one growth per level
     // of list nesting (bounded by the table count)
     for (uint32_t attempt = 0; attempt <= L.nt; attempt++) {
-        int rc = run(d, stream_bytes, stream_len, ends, spans, n, nullptr, nullptr, st);
+        int rc = run(d, stream_bytes, stream_len, ends, spans, head, n, nullptr, nullptr, st);
         if (rc) return rc;
         uint64_t got[TREE_MAX_T];
         if (hipMemcpyAsync(got, d->B.rowsd, sizeof(uint64_t) * TREE_MAX_T, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -587,30 +591,52 @@ void spec_tree_decoder_destroy(spec_tree_decoder *d) { delete d; }
 int spec_tree_decoder_index(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len,
                             const uint64_t *ends, uint64_t n, uint64_t *rows, void *stream) {
     if (!d) return SPEC_E_INVALID_ARGUMENT;
-    return index(d, stream_bytes, stream_len, ends, nullptr, n, rows, (hipStream_t)stream);
+    return index(d, stream_bytes, stream_len, ends, nullptr, 0, n, rows, (hipStream_t)stream);
+}
+
+// spec_tree_decoder_index over mpx frames (mpx/conn_reader.go:179-194): ends are frame ends, record i
+// is frames[ends[i-1] + 4, ends[i]).  The decoder remembers the head: spec_tree_decoder_decode after
+// it decodes the frames.
+int spec_tree_decoder_index_frames(spec_tree_decoder *d, const uint8_t *frames, uint64_t frames_len,
+                                   const uint64_t *ends, uint64_t n, uint64_t *rows, void *stream) {
+    if (!d) return SPEC_E_INVALID_ARGUMENT;
+    return index(d, frames, frames_len, ends, nullptr, 4, n, rows, (hipStream_t)stream);
 }
 
 int spec_tree_decoder_index_spans(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len,
                                   const spec_span *spans, uint64_t n, uint64_t *rows, void *stream) {
     if (!d || (n && !spans)) return SPEC_E_INVALID_ARGUMENT;
-    return index(d, stream_bytes, stream_len, nullptr, (const uint2 *)spans, n, rows, (hipStream_t)stream);
+    return index(d, stream_bytes, stream_len, nullptr, (const uint2 *)spans, 0, n, rows, (hipStream_t)stream);
 }
 
 int spec_tree_decoder_decode(spec_tree_decoder *d, void *const *columns, void *stream) {
     if (!d || !d->indexed || !columns) return SPEC_E_INVALID_ARGUMENT;
     const TreeBufs &B = d->B;
-    return run(d, B.stream, B.stream_len, B.ends, B.spans, B.n, columns, nullptr, (hipStream_t)stream);
+    return run(d, B.stream, B.stream_len, B.ends, B.spans, B.head, B.n, columns, nullptr, (hipStream_t)stream);
+}
+
+static int tree_run_impl(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends,
+                         uint32_t head, uint64_t n, void *const *columns, const uint64_t *col_rows,
+                         uint64_t *rows_out, void *stream) {
+    if (!d || !columns) return SPEC_E_INVALID_ARGUMENT;
+    const int rc = run(d, stream_bytes, stream_len, ends, nullptr, head, n, columns, col_rows, (hipStream_t)stream);
+    if (rc || !rows_out) return rc;
+    hipLaunchKernelGGL(rows_out_kernel, dim3(1), dim3(TREE_MAX_T), 0, (hipStream_t)stream,
+                       (const TreeDesc *)d->desc.p, (const TreeBufs *)d->bufs.p, rows_out);
+    return hipGetLastError() == hipSuccess ? SPEC_OK : SPEC_E_HIP;
 }
 
 int spec_tree_decoder_run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends,
                           uint64_t n, void *const *columns, const uint64_t *col_rows, uint64_t *rows_out,
                           void *stream) {
-    if (!d || !columns) return SPEC_E_INVALID_ARGUMENT;
-    const int rc = run(d, stream_bytes, stream_len, ends, nullptr, n, columns, col_rows, (hipStream_t)stream);
-    if (rc || !rows_out) return rc;
-    hipLaunchKernelGGL(rows_out_kernel, dim3(1), dim3(TREE_MAX_T), 0, (hipStream_t)stream,
-                       (const TreeDesc *)d->desc.p, (const TreeBufs *)d->bufs.p, rows_out);
-    return hipGetLastError() == hipSuccess ? SPEC_OK : SPEC_E_HIP;
+    return tree_run_impl(d, stream_bytes, stream_len, ends, 0, n, columns, col_rows, rows_out, stream);
+}
+
+// spec_tree_decoder_run over mpx frames (ends: frame ends, as spec_tree_decoder_index_frames)
+int spec_tree_decoder_run_frames(spec_tree_decoder *d, const uint8_t *frames, uint64_t frames_len,
+                                 const uint64_t *ends, uint64_t n, void *const *columns, const uint64_t *col_rows,
+                                 uint64_t *rows_out, void *stream) {
+    return tree_run_impl(d, frames, frames_len, ends, 4, n, columns, col_rows, rows_out, stream);
 }
 
 int spec_tree_decoder_capacity(const spec_tree_decoder *d, uint64_t *rows) {

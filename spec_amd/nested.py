@@ -34,12 +34,21 @@ class NestedColumns:
 
 
 class NestedDecoder:
-    """Workspace + total for one schema and batch; call index() then decode()."""
+    """Workspace + total for one schema and batch; call index() then decode().  head = 4: `stream`
+    holds mpx frames and `ends` their frame ends (the spec_decode_nested_frames* entry points)."""
 
-    def __init__(self, schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None):
+    def __init__(self, schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None,
+                 head: int = 0):
         _check_dev(stream, "stream", torch.uint8)
         _check_dev(ends, "ends", torch.int64)
+        if head not in (0, 4):
+            raise ValueError("head must be 0 (records back to back) or 4 (mpx frames)")
         self.schema, self.stream, self.ends = schema, stream, ends
+        self.head = head
+        self._fn = {"index": "spec_decode_nested_frames_index", "decode": "spec_decode_nested_frames",
+                    "onepass": "spec_decode_nested_frames_onepass"} if head else {
+                        "index": "spec_decode_nested_index", "decode": "spec_decode_nested",
+                        "onepass": "spec_decode_nested_onepass"}
         self.n = ends.numel()
         L = _lib.lib()
         ws = L.spec_decode_nested_workspace_size(self.n)
@@ -55,10 +64,11 @@ class NestedDecoder:
         self.items, self.item_status, self.item_cap = [], None, 0
 
     def index(self) -> torch.Tensor:
-        rc = _lib.lib().spec_decode_nested_index(C.byref(self.schema.c), _ptr(self.stream), self.stream.numel(),
-                                                 _ptr(self.ends), self.n, _ptr(self.workspace), self.ws_bytes,
-                                                 _ptr(self.total), _stream_handle(self.cuda_stream))
-        _lib.check(rc, "spec_decode_nested_index")
+        fn = self._fn["index"]
+        rc = getattr(_lib.lib(), fn)(C.byref(self.schema.c), _ptr(self.stream), self.stream.numel(),
+                                     _ptr(self.ends), self.n, _ptr(self.workspace), self.ws_bytes,
+                                     _ptr(self.total), _stream_handle(self.cuda_stream))
+        _lib.check(rc, fn)
         return self.total
 
     def reserve(self, m: int):
@@ -70,11 +80,12 @@ class NestedDecoder:
     def decode(self):
         outer = (C.c_void_p * max(1, len(self.outer)))(*[c.data_ptr() if c is not None else 0 for c in self.outer])
         items = (C.c_void_p * max(1, len(self.items)))(*[c.data_ptr() for c in self.items])
-        rc = _lib.lib().spec_decode_nested(C.byref(self.schema.c), _ptr(self.stream), self.stream.numel(),
-                                           _ptr(self.ends), self.n, outer, _ptr(self.status), _ptr(self.item_begin),
-                                           items, _ptr(self.item_status), self.item_cap, _ptr(self.workspace),
-                                           self.ws_bytes, _stream_handle(self.cuda_stream))
-        _lib.check(rc, "spec_decode_nested")
+        fn = self._fn["decode"]
+        rc = getattr(_lib.lib(), fn)(C.byref(self.schema.c), _ptr(self.stream), self.stream.numel(),
+                                     _ptr(self.ends), self.n, outer, _ptr(self.status), _ptr(self.item_begin),
+                                     items, _ptr(self.item_status), self.item_cap, _ptr(self.workspace),
+                                     self.ws_bytes, _stream_handle(self.cuda_stream))
+        _lib.check(rc, fn)
 
     def decode_onepass(self) -> torch.Tensor:
         """spec_decode_nested_onepass into the reserved item columns (no index call); returns the
@@ -82,11 +93,12 @@ class NestedDecoder:
         reserve(total) and call again."""
         outer = (C.c_void_p * max(1, len(self.outer)))(*[c.data_ptr() if c is not None else 0 for c in self.outer])
         items = (C.c_void_p * max(1, len(self.items)))(*[c.data_ptr() for c in self.items])
-        rc = _lib.lib().spec_decode_nested_onepass(
+        fn = self._fn["onepass"]
+        rc = getattr(_lib.lib(), fn)(
             C.byref(self.schema.c), _ptr(self.stream), self.stream.numel(), _ptr(self.ends), self.n, outer,
             _ptr(self.status), _ptr(self.item_begin), items, _ptr(self.item_status), self.item_cap,
             _ptr(self.workspace), self.ws_bytes, _ptr(self.total), _stream_handle(self.cuda_stream))
-        _lib.check(rc, "spec_decode_nested_onepass")
+        _lib.check(rc, fn)
         return self.total
 
     def result(self) -> NestedColumns:
@@ -95,11 +107,11 @@ class NestedDecoder:
 
 
 def decode_nested(schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None,
-                  onepass: bool = False, item_cap: int | None = None) -> NestedColumns:
+                  onepass: bool = False, item_cap: int | None = None, *, head: int = 0) -> NestedColumns:
     """Two-pass: index, size the item columns from the device total, decode.  onepass: decode
     into item_cap items (default 4 per record) in one pass; if the batch holds more, grow the
     item columns to the reported total and decode again."""
-    d = NestedDecoder(schema, stream, ends, cuda_stream)
+    d = NestedDecoder(schema, stream, ends, cuda_stream, head)
     if onepass:
         d.reserve(max(1, item_cap if item_cap is not None else 4 * d.n))
         total = int(d.decode_onepass().item())
@@ -111,6 +123,14 @@ def decode_nested(schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor
     d.reserve(total)
     d.decode()
     return d.result()
+
+
+def decode_nested_frames(schema: NestedSchema, frames: torch.Tensor, ends: torch.Tensor, cuda_stream=None,
+                         onepass: bool = False, item_cap: int | None = None) -> NestedColumns:
+    """decode_nested over mpx frames in place (mpx/conn_reader.go:179-194): `frames` is the received
+    buffer `[u32 BE size][message]...`, `ends` the frame ends frames_index[_device] reports.  String
+    and bytes spans are offsets into `frames`."""
+    return decode_nested(schema, frames, ends, cuda_stream, onepass, item_cap, head=4)
 
 
 class NestedEncoder:

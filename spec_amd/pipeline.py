@@ -54,6 +54,17 @@ class HostDecoder:
         _lib.check(rc, "spec_host_decoder_run")
         return self.h_out
 
+    def run_frames(self, h_frames: torch.Tensor, h_ends: torch.Tensor):
+        """decode() over mpx frames as the receive loop holds them (spec_host_decoder_run_frames):
+        h_frames: pinned uint8 `[u32 BE size][message]...`; h_ends: pinned int64 [n] frame ends
+        (frames_index).  Spans are offsets into h_frames."""
+        if h_ends.numel() != self.n:
+            raise ValueError("h_ends must hold n frame ends")
+        rc = _lib.lib().spec_host_decoder_run_frames(self._h, _ptr(h_frames), h_frames.numel(), _ptr(h_ends), self.n,
+                                                     _ptr(self.h_out))
+        _lib.check(rc, "spec_host_decoder_run_frames")
+        return self.h_out
+
     def chunk(self, k: int):
         """(r0, r1, [host column views [r1-r0, width]], host status view) of chunk k."""
         r0, r1, so = C.c_uint64(), C.c_uint64(), C.c_uint64()

@@ -273,17 +273,23 @@ class TreeDecoder:
             except Exception:
                 pass
 
-    def index(self, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None) -> list:
+    def index(self, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None, *,
+              _fn="spec_tree_decoder_index") -> list:
         if not (stream.is_cuda and ends.is_cuda and stream.dtype == torch.uint8 and ends.dtype == torch.int64):
             raise ValueError("stream uint8 and ends int64 device tensors")
         self._keep = (stream, ends)
         rows = (C.c_uint64 * len(self.tree.tables))()
-        rc = _lib.lib().spec_tree_decoder_index(self._h, C.c_void_p(stream.data_ptr()), stream.numel(),
-                                                 C.c_void_p(ends.data_ptr()), ends.numel(), rows,
-                                                 _stream_handle(cuda_stream))
-        _lib.check(rc, "spec_tree_decoder_index")
+        rc = getattr(_lib.lib(), _fn)(self._h, C.c_void_p(stream.data_ptr()), stream.numel(),
+                                      C.c_void_p(ends.data_ptr()), ends.numel(), rows, _stream_handle(cuda_stream))
+        _lib.check(rc, _fn)
         self.rows = [int(r) for r in rows]
         return self.rows
+
+    def index_frames(self, frames: torch.Tensor, ends: torch.Tensor, cuda_stream=None) -> list:
+        """index() over mpx frames in place (spec_tree_decoder_index_frames): `frames` is the
+        received buffer `[u32 BE size][message]...`, `ends` the frame ends frames_index[_device]
+        reports.  decode() after it decodes the frames; spans are offsets into `frames`."""
+        return self.index(frames, ends, cuda_stream, _fn="spec_tree_decoder_index_frames")
 
     def index_spans(self, stream: torch.Tensor, spans: torch.Tensor, cuda_stream=None) -> list:
         """index() over value spans (an `any` / `message` column, int32/uint32 [n, 2] or uint8
@@ -326,7 +332,7 @@ class TreeDecoder:
         return [int(x) for x in r]
 
     def run(self, stream: torch.Tensor, ends: torch.Tensor, cols: list, rows_out: torch.Tensor | None = None,
-            cuda_stream=None, col_rows=None) -> torch.Tensor:
+            cuda_stream=None, col_rows=None, *, _fn="spec_tree_decoder_run") -> torch.Tensor:
         """Decode a new batch into `cols` in one asynchronous pass (spec_tree_decoder_run): no
         host synchronisation; returns the device row counts (int64 [ntables], -1 where a list
         table outgrew the decoder's capacity or its columns, and below such a list: index() a
@@ -342,11 +348,16 @@ class TreeDecoder:
         self._keep = (stream, ends)
         ptrs = (C.c_void_p * len(cols))(*[c.data_ptr() if c is not None else 0 for c in cols])
         caps = (C.c_uint64 * len(self.tree.tables))(*(col_rows if col_rows is not None else self.column_capacity(cols)))
-        rc = _lib.lib().spec_tree_decoder_run(self._h, C.c_void_p(stream.data_ptr()), stream.numel(),
-                                               C.c_void_p(ends.data_ptr()), ends.numel(), ptrs, caps,
-                                               C.c_void_p(rows_out.data_ptr()), _stream_handle(cuda_stream))
-        _lib.check(rc, "spec_tree_decoder_run")
+        rc = getattr(_lib.lib(), _fn)(self._h, C.c_void_p(stream.data_ptr()), stream.numel(),
+                                      C.c_void_p(ends.data_ptr()), ends.numel(), ptrs, caps,
+                                      C.c_void_p(rows_out.data_ptr()), _stream_handle(cuda_stream))
+        _lib.check(rc, _fn)
         return rows_out
+
+    def run_frames(self, frames: torch.Tensor, ends: torch.Tensor, cols: list, rows_out: torch.Tensor | None = None,
+                   cuda_stream=None, col_rows=None) -> torch.Tensor:
+        """run() over mpx frames in place (spec_tree_decoder_run_frames; `ends`: frame ends)."""
+        return self.run(frames, ends, cols, rows_out, cuda_stream, col_rows, _fn="spec_tree_decoder_run_frames")
 
     def reserve(self, rows):
         """List-table capacities of at least rows[t] (spec_tree_decoder_reserve)."""
@@ -369,6 +380,13 @@ class TreeDecoder:
 def decode_tree(tree: Tree, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None) -> TreeColumns:
     d = TreeDecoder(tree)
     d.index(stream, ends, cuda_stream)
+    return d.decode(cuda_stream=cuda_stream)
+
+
+def decode_tree_frames(tree: Tree, frames: torch.Tensor, ends: torch.Tensor, cuda_stream=None) -> TreeColumns:
+    """decode_tree over mpx frames in place (`ends`: the frame ends frames_index[_device] reports)."""
+    d = TreeDecoder(tree)
+    d.index_frames(frames, ends, cuda_stream)
     return d.decode(cuda_stream=cuda_stream)
 
 
