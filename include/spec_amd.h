@@ -489,6 +489,29 @@ int spec_decode_frames(const spec_schema *schema, const uint8_t *frames, uint64_
 int spec_decode_frames_errors(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
                               const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes,
                               void *const *columns, uint8_t *status, uint64_t *errmask, void *stream);
+/* ---- optional fields: HasField masks ----
+ * Every generated reader has a HasX() per field, scalars included: m.msg.HasField(tag)
+ * (internal/lang/generator/message.go:203-212, internal/types/msg.go:106-111).
+ * spec_decode_flat_present: spec_decode_flat plus present[i] bit f = m.HasField(tag_f) on the m of
+ * OpenMessageErr(record_i): the table lookup finds the tag and its end offset lies within the data
+ * (0 <= end <= dataSize).  An entry with end == 0 is PRESENT (its getter returns zero and never
+ * errs); an entry with end > dataSize is absent; a record whose status is not OK is the empty
+ * Message{}: every bit 0.  Unsorted or duplicate tables give what the reference's binary search
+ * gives.  Layout as errmask: one word per record up to 64 fields, else ceil(nfields / 64) words per
+ * record, word-major (word c of record i at present[c * n + i], bit f = field 64 c + f); bits at or
+ * above nfields are 0.  errmask may be NULL, or takes spec_decode_flat_errors' masks; present must
+ * not be NULL and the schema must have fields.  A Writer that skipped setters leaves a table holding
+ * a subset of the schema's tags: the schema-specialised kernels decode such a record on their fast
+ * path (small tables, at most 24 fields), the same columns and status as spec_decode_flat.
+ * spec_decode_frames_present: the same over mpx frames in place, with spec_decode_frames_errors'
+ * range arguments (word c of record r at present[c * r1 + r]). */
+int spec_decode_flat_present(const spec_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                             const uint64_t *ends, uint64_t n, void *const *columns, uint8_t *status,
+                             uint64_t *errmask, uint64_t *present, void *stream);
+int spec_decode_frames_present(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                               const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes,
+                               void *const *columns, uint8_t *status, uint64_t *errmask, uint64_t *present,
+                               void *stream);
 /* spec_frames_index_device: spec_frames_index on a DEVICE buffer (4-byte aligned), with the same
  * results: ends[0, min(frames, cap)), *count, *consumed (device uint64) and *status (device int32:
  * SPEC_OK, or SPEC_E_CAPACITY when more than cap complete frames exist — then *count = cap).  The
@@ -786,6 +809,30 @@ int spec_encode_flat_frames(const spec_schema *schema, const void *const *column
                             const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n,
                             uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends,
                             void *workspace, size_t workspace_size, uint64_t *total, void *stream);
+
+/* spec_encode_flat_present: a generated Write() that calls only some setters
+ * (internal/tests/pkg1/object.go:85-167).  For record i exactly
+ *     w.Field(tag_f).<Kind_f>(column_f[i])  for the f whose bit of present is set, in schema order
+ *     w.Build()
+ * present has spec_decode_flat_present's layout (word c of record i at present[c * n + i]) and must
+ * not be NULL; bits at or above nfields are ignored.  The table holds only the written fields, at
+ * their sorted positions among the written ones (the tie rule of internal/writer/stack_msg.go:37-61);
+ * IsBigMessage is per record (internal/format/msg.go:43-61): a written tag > 255 or a data size
+ * > 65535.  No field written gives the 3-byte message 00 00 50.  An absent field's column value is
+ * never read: a garbage string/bytes span there is no encoder error.  out == NULL computes only
+ * *total.  Workspace spec_encode_flat_workspace_size(n); capacity, all-ones-on-error and return
+ * codes as spec_encode_flat; asynchronous; nothing outside out[0, *total) is written, at any byte
+ * alignment of out.  Runs the run-time kernels for every schema.
+ * spec_encode_flat_present_frames: the same behind mpx frame heads, as spec_encode_flat_frames. */
+int spec_encode_flat_present(const spec_schema *schema, const void *const *columns,
+                             const uint8_t *const *heaps, const uint64_t *heap_lens, const uint64_t *present,
+                             uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *ends, void *workspace,
+                             size_t workspace_size, uint64_t *total, void *stream);
+int spec_encode_flat_present_frames(const spec_schema *schema, const void *const *columns,
+                                    const uint8_t *const *heaps, const uint64_t *heap_lens,
+                                    const uint64_t *present, uint64_t n, uint8_t *frames, uint64_t frames_cap,
+                                    uint64_t *frame_ends, void *workspace, size_t workspace_size, uint64_t *total,
+                                    void *stream);
 
 /* ---- nested encode (list<message>) ----
  * For every record i, what a generated Write() does (writer_list_msg.go:8-47): the outer

@@ -150,17 +150,25 @@ class MessageBatch {
     uint64_t Len() const { return n_; }
     template <class T>
     std::vector<T> Get(size_t f, Stream &s) const { return cols_[f].ToHost<T>(s); }
+    // The generated HasX() of every field (m.msg.HasField(tag), internal/types/msg.go:106-111), filled
+    // by OpenMessageBatch / OpenMessageFrames with present = true: uint64 words, bit f & 63 of word
+    // (f >> 6) * Len() + i = record i has field f.  Empty otherwise.
+    const DeviceBuffer &Present() const { return present_; }
 
   private:
-    friend MessageBatch OpenMessageBatch(const Schema &, const Batch &, Stream &);
-    friend MessageBatch OpenMessageFrames(const Schema &, const Frames &, Stream &);
+    friend MessageBatch OpenMessageBatch(const Schema &, const Batch &, Stream &, bool);
+    friend MessageBatch OpenMessageFrames(const Schema &, const Frames &, Stream &, bool);
     std::vector<DeviceBuffer> cols_;
-    DeviceBuffer status_;
+    DeviceBuffer status_, present_;
     uint64_t n_ = 0;
 };
 
+// the mask words of a batch of n records: one per record and 64 fields
+inline size_t PresentWords(const Schema &schema, uint64_t n) { return (size_t)((schema.Len() + 63) / 64) * n; }
+
 // For every record: m, err := spec.OpenMessageErr(b); status = class(err); column_f = m.<Kind_f>(tag_f).
-inline MessageBatch OpenMessageBatch(const Schema &schema, const Batch &b, Stream &s) {
+// present: also the HasField masks (MessageBatch::Present, spec_decode_flat_present).
+inline MessageBatch OpenMessageBatch(const Schema &schema, const Batch &b, Stream &s, bool present = false) {
     MessageBatch m;
     m.n_ = b.n;
     std::vector<void *> ptrs;
@@ -170,6 +178,14 @@ inline MessageBatch OpenMessageBatch(const Schema &schema, const Batch &b, Strea
     }
     m.status_ = DeviceBuffer(b.n + 1);
     spec_schema c = schema.C();
+    if (present) {
+        m.present_ = DeviceBuffer(PresentWords(schema, b.n) * 8 + 8);
+        Check(spec_decode_flat_present(&c, (const uint8_t *)b.stream.data(), b.len, (const uint64_t *)b.ends.data(),
+                                       b.n, ptrs.data(), (uint8_t *)m.status_.data(), nullptr,
+                                       (uint64_t *)m.present_.data(), s.get()),
+              "spec_decode_flat_present");
+        return m;
+    }
     Check(spec_decode_flat(&c, (const uint8_t *)b.stream.data(), b.len, (const uint64_t *)b.ends.data(), b.n,
                            ptrs.data(), (uint8_t *)m.status_.data(), s.get()),
           "spec_decode_flat");
@@ -195,7 +211,7 @@ struct Frames {
 // OpenMessageBatch over frames where they lie (connReader.readMessage's frames, conn_reader.go:179-194:
 // record i = bytes[ends[i-1] + 4, ends[i])): no unframed copy.  String and bytes spans are offsets
 // into f.bytes.
-inline MessageBatch OpenMessageFrames(const Schema &schema, const Frames &f, Stream &s) {
+inline MessageBatch OpenMessageFrames(const Schema &schema, const Frames &f, Stream &s, bool present = false) {
     MessageBatch m;
     m.n_ = f.n;
     std::vector<void *> ptrs;
@@ -205,6 +221,14 @@ inline MessageBatch OpenMessageFrames(const Schema &schema, const Frames &f, Str
     }
     m.status_ = DeviceBuffer(f.n + 1);
     spec_schema c = schema.C();
+    if (present) {
+        m.present_ = DeviceBuffer(PresentWords(schema, f.n) * 8 + 8);
+        Check(spec_decode_frames_present(&c, (const uint8_t *)f.bytes.data(), f.len, (const uint64_t *)f.ends.data(),
+                                         0, f.n, 0, ptrs.data(), (uint8_t *)m.status_.data(), nullptr,
+                                         (uint64_t *)m.present_.data(), s.get()),
+              "spec_decode_frames_present");
+        return m;
+    }
     Check(spec_decode_frames(&c, (const uint8_t *)f.bytes.data(), f.len, (const uint64_t *)f.ends.data(), 0, f.n, 0,
                              ptrs.data(), (uint8_t *)m.status_.data(), s.get()),
           "spec_decode_frames");
@@ -227,11 +251,40 @@ class MessageBatchWriter {
         return *this;
     }
 
+    // A Write() that calls only some setters (internal/tests/pkg1/object.go:85-167): record i writes
+    // exactly the fields whose bit of `present` is set (MessageBatch::Present's layout, PresentWords
+    // words); Build and BuildFrames then run spec_encode_flat_present[_frames].  The buffer must
+    // outlive them.
+    MessageBatchWriter &SetPresent(const DeviceBuffer &present) {
+        if (present.size() < PresentWords(schema_, n_) * 8) throw Error(SPEC_E_INVALID_ARGUMENT, "SetPresent");
+        present_ = (const uint64_t *)present.data();
+        return *this;
+    }
+
     // Sizes, then (after one host sync for the total) the bytes.
     Batch Build(Stream &s) {
         spec_schema c = schema_.C();
         const size_t ws = spec_encode_flat_workspace_size(n_);
         DeviceBuffer work(ws), total(8);
+        if (present_) {
+            Check(spec_encode_flat_present(&c, cols_.data(), heaps_.data(), lens_.data(), present_, n_, nullptr, 0,
+                                           nullptr, work.data(), ws, (uint64_t *)total.data(), s.get()),
+                  "spec_encode_flat_present");
+            uint64_t t = 0;
+            total.CopyTo(&t, 8, s);
+            s.Sync();
+            if (t == ~0ull) throw Error(SPEC_E_INVALID_ARGUMENT, "MessageBatchWriter::Build (encoder error)");
+            Batch b;
+            b.stream = DeviceBuffer(t ? t : 1);
+            b.ends = DeviceBuffer(n_ * 8 + 8);
+            b.len = t;
+            b.n = n_;
+            Check(spec_encode_flat_present(&c, cols_.data(), heaps_.data(), lens_.data(), present_, n_,
+                                           (uint8_t *)b.stream.data(), t, (uint64_t *)b.ends.data(), work.data(), ws,
+                                           (uint64_t *)total.data(), s.get()),
+                  "spec_encode_flat_present");
+            return b;
+        }
         Check(spec_encode_flat_size(&c, cols_.data(), n_, work.data(), ws, (uint64_t *)total.data(), s.get()),
               "spec_encode_flat_size");
         uint64_t t = 0;
@@ -259,6 +312,25 @@ class MessageBatchWriter {
         spec_schema c = schema_.C();
         const size_t ws = spec_encode_flat_workspace_size(n_);
         DeviceBuffer work(ws), total(8);
+        if (present_) {
+            Check(spec_encode_flat_present_frames(&c, cols_.data(), heaps_.data(), lens_.data(), present_, n_, nullptr,
+                                                  0, nullptr, work.data(), ws, (uint64_t *)total.data(), s.get()),
+                  "spec_encode_flat_present_frames");
+            uint64_t t = 0;
+            total.CopyTo(&t, 8, s);
+            s.Sync();
+            if (t == ~0ull) throw Error(SPEC_E_INVALID_ARGUMENT, "MessageBatchWriter::BuildFrames (encoder error)");
+            Frames f;
+            f.len = t;
+            f.n = n_;
+            f.bytes = DeviceBuffer(f.len + 1);
+            f.ends = DeviceBuffer(n_ * 8 + 8);
+            Check(spec_encode_flat_present_frames(&c, cols_.data(), heaps_.data(), lens_.data(), present_, n_,
+                                                  (uint8_t *)f.bytes.data(), f.len, (uint64_t *)f.ends.data(),
+                                                  work.data(), ws, (uint64_t *)total.data(), s.get()),
+                  "spec_encode_flat_present_frames");
+            return f;
+        }
         Check(spec_encode_flat_size(&c, cols_.data(), n_, work.data(), ws, (uint64_t *)total.data(), s.get()),
               "spec_encode_flat_size");
         uint64_t t = 0;
@@ -285,6 +357,7 @@ class MessageBatchWriter {
   private:
     Schema schema_;
     uint64_t n_;
+    const uint64_t *present_ = nullptr;
     std::vector<const void *> cols_;
     std::vector<const uint8_t *> heaps_;
     std::vector<uint64_t> lens_;

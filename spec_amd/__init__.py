@@ -7,10 +7,11 @@ decoded into SoA columns / encoded from them by hand-written gfx950 kernels
 """
 from ._lib import LIB_PATH, SpecError, header_symbols, lib, set_jit
 from .batch import (PARSE_LIST, PARSE_MESSAGE, PARSE_VALUE, Columns, Decoder, Encoder, alloc_columns, decode_flat,
-                    decode_flat_errors, encode_flat, encode_flat_frames, parse_messages)
+                    decode_flat_errors, decode_flat_present, encode_flat, encode_flat_frames, encode_flat_present,
+                    parse_messages)
 from . import lz4
 from .lz4 import Lz4Writer, compress_frame, frame_bound
-from .frames import (decode_frames, decode_frames_errors, frames_index, frames_index_device, make_frames, make_frames_device,
+from .frames import (decode_frames, decode_frames_errors, decode_frames_present, frames_index, frames_index_device, make_frames, make_frames_device,
                      write_frames)
 from .pipeline import HostDecoder
 from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, decode_nested_frames,
@@ -27,4 +28,5 @@ __all__ = [
     "encode_nested", "encode_nested_frames", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
     "decode_values", "encode_tree", "encode_tree_frames", "pkg1_message", "pkg1_tree", "tree_rows",
     "decode_frames_errors", "decode_nested_frames", "decode_tree_frames",
+    "decode_flat_present", "decode_frames_present", "encode_flat_present",
 ]

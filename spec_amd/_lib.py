@@ -263,6 +263,16 @@ def _declare(L):
     L.spec_tree_decoder_index_frames.argtypes = L.spec_tree_decoder_index.argtypes
     L.spec_tree_decoder_run_frames.argtypes = L.spec_tree_decoder_run.argtypes
     L.spec_host_decoder_run_frames.argtypes = L.spec_host_decoder_run.argtypes
+    # optional fields: the HasField masks on decode (after errmask), the presence masks on encode
+    # (after heap_lens)
+    L.spec_decode_flat_present.argtypes = [C.POINTER(SpecSchema), vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), vp,
+                                           vp, vp, vp]
+    L.spec_decode_frames_present.argtypes = [C.POINTER(SpecSchema), vp, C.c_uint64, vp, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, C.POINTER(vp), vp, vp, vp, vp]
+    L.spec_encode_flat_present.argtypes = [C.POINTER(SpecSchema), C.POINTER(vp), C.POINTER(vp),
+                                           C.POINTER(C.c_uint64), vp, C.c_uint64, vp, C.c_uint64, vp, vp,
+                                           C.c_size_t, vp, vp]
+    L.spec_encode_flat_present_frames.argtypes = L.spec_encode_flat_present.argtypes
 
 
 def strerror(rc: int) -> str:

@@ -108,6 +108,37 @@ def decode_flat_errors(schema: Schema, stream: torch.Tensor, ends: torch.Tensor,
     return Columns(schema, cols, st), (em[0, :n] if words == 1 else em[:, :n])
 
 
+def _mask_words(schema: Schema) -> int:
+    return max(1, (len(schema) + 63) // 64)
+
+
+def _mask_view(mask: torch.Tensor, words: int, n: int):
+    m = mask.view(words, -1)
+    return m[0, :n] if words == 1 else m[:, :n]
+
+
+def decode_flat_present(schema: Schema, stream: torch.Tensor, ends: torch.Tensor, *, errors: bool = False,
+                        cuda_stream=None):
+    """spec_decode_flat_present: decode_flat plus the per-record HasField mask (bit f: m.HasField(tag_f),
+    internal/types/msg.go:106-111; an entry with end 0 is present, a record that does not open has no
+    bit) -> (Columns, present[, errmask]).  The masks have decode_flat_errors' dtype and shape:
+    int64 [n], or [ceil(nfields / 64), n] for more than 64 fields."""
+    _check_dev(stream, "stream", torch.uint8)
+    _check_dev(ends, "ends", torch.int64)
+    n = ends.numel()
+    cols = alloc_columns(schema, n, stream.device)
+    st = torch.empty(n, dtype=torch.uint8, device=stream.device)
+    words = _mask_words(schema)
+    pm = torch.empty((words, max(n, 1)), dtype=torch.int64, device=stream.device)
+    em = torch.empty((words, max(n, 1)), dtype=torch.int64, device=stream.device) if errors else None
+    ptrs = (C.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+    rc = _lib.lib().spec_decode_flat_present(C.byref(schema.c), _ptr(stream), stream.numel(), _ptr(ends), n, ptrs,
+                                              _ptr(st), _ptr(em), _ptr(pm), _stream_handle(cuda_stream))
+    _lib.check(rc, "spec_decode_flat_present")
+    out = (Columns(schema, cols, st), _mask_view(pm, words, n))
+    return out + (_mask_view(em, words, n),) if errors else out
+
+
 class Decoder:
     """Pre-bound spec_decode_flat call (arguments marshalled once) for repeated launches."""
 
@@ -195,6 +226,62 @@ class Encoder:
                                                 _ptr(out), out.numel(), _ptr(ends), _ptr(self.workspace),
                                                 self.ws_bytes, _ptr(self.total), _stream_handle(cuda_stream))
         _lib.check(rc, "spec_encode_flat_frames")
+
+
+    def _present(self, present: torch.Tensor):
+        _check_dev(present, "present", torch.int64)
+        if present.numel() < _mask_words(self.schema) * self.n:
+            raise ValueError("present: one int64 word per record and 64 fields")
+        return present
+
+    def _call_present(self, fn, cols, heaps, present, out, ends, cuda_stream):
+        hp, hl, _keep = self._heapptrs(heaps)
+        rc = getattr(_lib.lib(), fn)(C.byref(self.schema.c), self._colptrs(cols), hp, hl, _ptr(self._present(present)),
+                                     self.n, _ptr(out), out.numel() if out is not None else 0, _ptr(ends),
+                                     _ptr(self.workspace), self.ws_bytes, _ptr(self.total),
+                                     _stream_handle(cuda_stream))
+        _lib.check(rc, fn)
+
+    def size_present(self, cols, heaps: dict, present: torch.Tensor, frames: bool = False, cuda_stream=None):
+        """spec_encode_flat_present[_frames] with out = NULL: the sizing passes of a batch whose record i
+        writes only the fields of present[i] (decode_flat_present's layout); returns the device total."""
+        self._call_present("spec_encode_flat_present_frames" if frames else "spec_encode_flat_present", cols, heaps,
+                           present, None, None, cuda_stream)
+        return self.total
+
+    def encode_present_into(self, cols, heaps: dict, present: torch.Tensor, out: torch.Tensor, ends: torch.Tensor,
+                            cuda_stream=None):
+        """spec_encode_flat_present: all passes; writes out[:total], ends[n] and self.total (device)."""
+        _check_dev(out, "out", torch.uint8)
+        _check_dev(ends, "ends", torch.int64)
+        self._call_present("spec_encode_flat_present", cols, heaps, present, out, ends, cuda_stream)
+
+    def encode_present_frames_into(self, cols, heaps: dict, present: torch.Tensor, out: torch.Tensor,
+                                   ends: torch.Tensor, cuda_stream=None):
+        """spec_encode_flat_present_frames: encode_present_into with every record behind its mpx frame
+        head; ends are the frame ends, self.total the framed size."""
+        _check_dev(out, "out", torch.uint8)
+        _check_dev(ends, "ends", torch.int64)
+        self._call_present("spec_encode_flat_present_frames", cols, heaps, present, out, ends, cuda_stream)
+
+
+def encode_flat_present(schema: Schema, cols, heaps: dict, present: torch.Tensor, n: int | None = None,
+                        frames: bool = False, cuda_stream=None):
+    """Encode a batch whose record i writes only the fields whose bit of present[i] is set (a
+    generated Write() that skips setters) -> (stream uint8[total], ends int64[n]) on the device;
+    frames=True: the mpx frames and their ends.  present: int64 [n], or [ceil(nfields / 64), n]."""
+    if n is None:
+        n = cols[0].shape[0] if cols else 0
+    dev = cols[0].device if cols else torch.device("cuda")
+    enc = Encoder(schema, n, dev)
+    total = int(enc.size_present(cols, heaps, present, frames, cuda_stream).item())
+    if total < 0:  # ~0: an encoder error (a written string/bytes span outside its heap or > MaxSize)
+        raise _lib.SpecError(-1, "spec_encode_flat_present: encoder error")
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    ends = torch.empty(n, dtype=torch.int64, device=dev)
+    (enc.encode_present_frames_into if frames else enc.encode_present_into)(cols, heaps, present, out, ends,
+                                                                            cuda_stream)
+    return out[:total], ends
 
 
 def encode_flat(schema: Schema, cols, heaps: dict, n: int | None = None, cuda_stream=None):

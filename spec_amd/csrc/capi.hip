@@ -182,7 +182,8 @@ void fill_enc_fields(spec::EncFields &e, const spec_schema *schema, const void *
     table_order(schema, e.order);
 }
 
-void fill_encode_args(spec::EncodeArgs &a, const spec_schema *schema, const void *const *columns, uint64_t n) {
+template <class A>
+void fill_encode_args(A &a, const spec_schema *schema, const void *const *columns, uint64_t n) {
     memset(&a, 0, sizeof(a));
     a.n = n;
     fill_enc_fields(a.f, schema, columns);
@@ -199,7 +200,8 @@ size_t enc_ws_sums(uint64_t n) {
 // A schema with more than SPEC_KFIELDS fields: its field set (tags, kinds, table positions,
 // columns, heaps) written into the workspace after the block sums, from a pinned slot on the
 // call's stream; the kernel argument holds the pointers.
-int fill_wide_encode_args(spec::WideEncodeArgs &a, const spec_schema *schema, const void *const *columns,
+template <class A>
+int fill_wide_encode_args(A &a, const spec_schema *schema, const void *const *columns,
                           const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n, void *workspace,
                           hipStream_t st) {
     memset(&a, 0, sizeof(a));
@@ -236,6 +238,26 @@ int fill_wide_encode_args(spec::WideEncodeArgs &a, const spec_schema *schema, co
     a.f.heap_lens = (const uint64_t *)(dev + o_lens);
     const hipError_t e = upload_async(dev, h.data(), bytes, st);
     return e == hipSuccess ? SPEC_OK : hip_rc(e);
+}
+
+// spec_encode_flat_present (frame_head 0) and spec_encode_flat_present_frames (4): the run-time
+// encoder's passes over a field set with the per-record presence masks; out == NULL sizes only
+template <class A>
+int encode_present_launch(A &a, const uint64_t *present, uint64_t n, uint8_t *out, uint64_t out_cap,
+                                 uint64_t *ends, void *workspace, uint64_t *total, hipStream_t st, uint32_t frame_head,
+                                 int (*size)(const A &, hipStream_t), int (*write)(const A &, hipStream_t)) {
+    a.f.present = present;
+    a.f.stride = n;
+    a.check_heaps = 1;
+    a.frame_head = frame_head;
+    a.out = out;
+    a.out_cap = out ? out_cap : 0;
+    a.ends = ends;
+    a.block_sums = (uint64_t *)workspace;
+    a.total = total;
+    if (size(a, st)) return hip_rc(hipGetLastError());
+    if (out && write(a, st)) return hip_rc(hipGetLastError());
+    return SPEC_OK;
 }
 
 } // namespace
@@ -405,9 +427,12 @@ int spec_copy_d2d(void *dst, const void *src, size_t bytes, void *stream) {
 
 static int decode_flat_impl(const spec_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
                             const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes, uint32_t head,
-                            void *const *columns, uint8_t *status, void *stream, uint64_t *errmask = nullptr) {
+                            void *const *columns, uint8_t *status, void *stream, uint64_t *errmask = nullptr,
+                            uint64_t *present = nullptr, bool want_present = false) {
     int rc = check_schema(schema);
     if (rc) return rc;
+    // spec_decode_*_present: a schema with fields, and a mask to write them to
+    if (want_present && (schema->nfields == 0 || !present)) return SPEC_E_INVALID_ARGUMENT;
     if (r1 < r0) return SPEC_E_INVALID_ARGUMENT;
     if (r1 == r0) return SPEC_OK;
     if (!ends || !columns || (!stream_bytes && stream_len)) return SPEC_E_INVALID_ARGUMENT;
@@ -429,16 +454,18 @@ static int decode_flat_impl(const spec_schema *schema, const uint8_t *stream_byt
         // a wide schema: the generic kernel once per chunk of SPEC_KFIELDS fields, each chunk's
         // getters against the record's whole table (ranks in the full Writer table); chunk 0
         // writes the status (OpenMessageErr, the same for every chunk), chunk c the errmask words
-        // errmask[c * r1 + r] (bit f = field 64 c + f)
+        // errmask[c * r1 + r] (bit f = field 64 c + f), and likewise the present words
         for (uint32_t f0 = 0; f0 < schema->nfields; f0 += SPEC_KFIELDS) {
             fill_field_set(a.f, schema, columns, f0 ? nullptr : status, f0, f0 + SPEC_KFIELDS);
             a.f.errmask = errmask ? errmask + (uint64_t)(f0 / SPEC_KFIELDS) * r1 : nullptr;
+            a.f.present = present ? present + (uint64_t)(f0 / SPEC_KFIELDS) * r1 : nullptr;
             if (spec::launch_decode_flat(a, avg, (hipStream_t)stream)) return hip_rc(hipGetLastError());
         }
         return SPEC_OK;
     }
     fill_field_set(a.f, schema, columns, status);
     a.f.errmask = errmask;
+    a.f.present = present;
     // field error masks: the schema-specialised kernel's errmask variant (or the generic path)
     int j = spec::jit_launch_decode_flat(schema, a, avg, (hipStream_t)stream);
     if (j < 0) return hip_rc(hipGetLastError());
@@ -478,6 +505,23 @@ int spec_decode_frames_errors(const spec_schema *schema, const uint8_t *frames, 
     if (!errmask && r1 > r0) return SPEC_E_INVALID_ARGUMENT;
     return decode_flat_impl(schema, frames, frames_len, ends, r0, r1, range_bytes, 4, columns, status, stream,
                             errmask);
+}
+
+// spec_decode_flat plus the per-record HasField masks (m.HasField(tag), internal/types/msg.go:106-111)
+int spec_decode_flat_present(const spec_schema *schema, const uint8_t *stream_bytes, uint64_t stream_len,
+                             const uint64_t *ends, uint64_t n, void *const *columns, uint8_t *status,
+                             uint64_t *errmask, uint64_t *present, void *stream) {
+    return decode_flat_impl(schema, stream_bytes, stream_len, ends, 0, n, 0, 0, columns, status, stream, errmask,
+                            present, true);
+}
+
+// spec_decode_flat_present over mpx frames in place
+int spec_decode_frames_present(const spec_schema *schema, const uint8_t *frames, uint64_t frames_len,
+                               const uint64_t *ends, uint64_t r0, uint64_t r1, uint64_t range_bytes,
+                               void *const *columns, uint8_t *status, uint64_t *errmask, uint64_t *present,
+                               void *stream) {
+    return decode_flat_impl(schema, frames, frames_len, ends, r0, r1, range_bytes, 4, columns, status, stream,
+                            errmask, present, true);
 }
 
 // mpx framing, mpx/conn_reader.go:179-194 (read) / mpx/conn_writer.go:84-97 (write):
@@ -938,6 +982,58 @@ int spec_encode_nested_frames(const spec_nested_schema *schema, const void *cons
 }
 
 size_t spec_encode_flat_workspace_size(uint64_t n) { return enc_ws_sums(n) + WIDE_FIELDS_BYTES; }
+
+// spec_encode_flat_present[_frames]: argument checks, then encode_present_launch
+static int encode_flat_present_impl(const spec_schema *schema, const void *const *columns, const uint8_t *const *heaps,
+                                    const uint64_t *heap_lens, const uint64_t *present, uint64_t n, uint8_t *out,
+                                    uint64_t out_cap, uint64_t *ends, void *workspace, size_t workspace_size,
+                                    uint64_t *total, void *stream, uint32_t frame_head) {
+    int rc = check_schema(schema);
+    if (rc) return rc;
+    if (schema->nfields == 0 || !present || !columns || !workspace || !total || (n && out && !ends))
+        return SPEC_E_INVALID_ARGUMENT;
+    if (workspace_size < spec_encode_flat_workspace_size(n)) return SPEC_E_WORKSPACE;
+    for (uint32_t f = 0; f < schema->nfields; f++) {
+        const int k = schema->fields[f].kind;
+        if ((k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) && (!heaps || !heap_lens || (!heaps[f] && heap_lens[f])))
+            return SPEC_E_INVALID_ARGUMENT;
+    }
+    if (schema->nfields > SPEC_KFIELDS) {
+        spec::WidePresentEncodeArgs w{};
+        if ((rc = fill_wide_encode_args(w, schema, columns, heaps, heap_lens, n, workspace, (hipStream_t)stream)))
+            return rc;
+        return encode_present_launch(w, present, n, out, out_cap, ends, workspace, total, (hipStream_t)stream,
+                                     frame_head, spec::launch_encode_wide_present_size,
+                                     spec::launch_encode_wide_present_write);
+    }
+    spec::PresentEncodeArgs a{};
+    fill_encode_args(a, schema, columns, n);
+    for (uint32_t f = 0; f < schema->nfields; f++) {
+        const int k = schema->fields[f].kind;
+        if (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) {
+            a.f.heaps[f] = heaps[f];
+            a.f.heap_lens[f] = heap_lens[f];
+        }
+    }
+    return encode_present_launch(a, present, n, out, out_cap, ends, workspace, total, (hipStream_t)stream, frame_head,
+                                 spec::launch_encode_present_size, spec::launch_encode_present_write);
+}
+
+int spec_encode_flat_present(const spec_schema *schema, const void *const *columns, const uint8_t *const *heaps,
+                             const uint64_t *heap_lens, const uint64_t *present, uint64_t n, uint8_t *out,
+                             uint64_t out_cap, uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total,
+                             void *stream) {
+    return encode_flat_present_impl(schema, columns, heaps, heap_lens, present, n, out, out_cap, ends, workspace,
+                                    workspace_size, total, stream, 0);
+}
+
+int spec_encode_flat_present_frames(const spec_schema *schema, const void *const *columns,
+                                    const uint8_t *const *heaps, const uint64_t *heap_lens, const uint64_t *present,
+                                    uint64_t n, uint8_t *frames, uint64_t frames_cap, uint64_t *frame_ends,
+                                    void *workspace, size_t workspace_size, uint64_t *total, void *stream) {
+    return encode_flat_present_impl(schema, columns, heaps, heap_lens, present, n, frames, frames_cap, frame_ends,
+                                    workspace, workspace_size, total, stream, 4);
+}
 
 int spec_encode_flat_size(const spec_schema *schema, const void *const *columns, uint64_t n,
                           void *workspace, size_t workspace_size, uint64_t *total, void *stream) {

@@ -36,6 +36,7 @@ namespace spec {
 struct FieldSet {
     uint8_t *status;
     uint64_t *errmask; // optional: bit f = field f's <Kind>Err getter errs
+    uint64_t *present; // the PRESENT kernels only: bit f = m.HasField(tag f) (internal/types/msg.go:106-111)
     uint32_t nfields;
     uint16_t tags[SPEC_KFIELDS];
     uint8_t kinds[SPEC_KFIELDS];
@@ -555,22 +556,27 @@ __device__ __forceinline__ long long rec_field_end(const Src &s, const RecInfo &
 
 // Parse record r occupying [rs, re) of the source into fs's columns; to_stream converts a
 // source position to a stream offset (string/bytes spans).  Kind K_LIST fields are skipped.
-template <class Src>
+// PRESENT: also fs.present[r], bit f = m.HasField(tag f) on the m of OpenMessageErr: the lookup
+// finds the tag and its end lies within the data (an entry with end 0 is present; a record
+// that does not open is the empty Message: no bit).
+template <bool PRESENT = false, class Src>
 __device__ __forceinline__ void decode_record_generic(const Src &s, typename Src::pos_t rs, typename Src::pos_t re,
                                                       uint64_t r, const FieldSet &fs, long long to_stream) {
     using pos_t = typename Src::pos_t;
     const RecInfo ri = rec_open(s, rs, re);
     if (fs.status) fs.status[r] = (uint8_t)ri.tr.st;
     const pos_t dstart = (pos_t)ri.tr.dstart;
-    uint64_t errs = 0;
+    uint64_t errs = 0, pres = 0;
     for (uint32_t f = 0; f < fs.nfields; f++) {
         const uint32_t kind = fs.kinds[f];
         if (kind == K_LIST) continue;
         const long long end = rec_field_end(s, ri, fs.tags[f], fs.rank[f]);
         const bool ok = decode_store(s, kind, dstart, end, to_stream, fs.cols[f], r);
         if (!ok && f < 64) errs |= 1ull << f;
+        if constexpr (PRESENT) pres |= (end >= 0 && f < 64) ? 1ull << f : 0ull;
     }
     if (fs.errmask) fs.errmask[r] = errs;
+    if constexpr (PRESENT) fs.present[r] = pres;
 }
 
 // ---- fast path: compile-time schema ------------------------------------------------------
@@ -796,10 +802,17 @@ struct WideField {
     }
 };
 
+// The bits a record's decode collects besides its columns: the <Kind>Err outcomes (ERR kernels) and
+// the HasField bits (PRESENT kernels), both in schema order.
+struct RecMasks {
+    uint64_t errs = 0, pres = 0;
+};
+
 // table entries [J0, J1): false when the record needs the generic path
-template <class Spec, int J0, int J1, bool ERR>
+// PRESENT: the table holds every tag, so HasField(tag) is "its end lies within the data".
+template <class Spec, int J0, int J1, bool ERR, bool PRESENT = false>
 __device__ __forceinline__ bool wide_batch(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                           const FieldSet &fs, long long to_stream, uint64_t &errs) {
+                                           const FieldSet &fs, long long to_stream, RecMasks &m) {
     constexpr int NB = J1 - J0;
     constexpr int ESZ = Spec::big ? 6 : 3;
     constexpr int NC = (ESZ * NB + 7) / 8, NQ = NC + 1;
@@ -827,39 +840,132 @@ __device__ __forceinline__ bool wide_batch(const LdsSrc &s, int ts, int ds, uint
         }
     }
     if (!hit) return false;
+    if constexpr (PRESENT) {
+#pragma unroll
+        for (int k = 0; k < NB; k++) m.pres |= ends[k] <= dsize ? 1ull << Spec::order[J0 + k] : 0ull;
+    }
     Win w[NB];
     int e[NB], lo[NB];
     WideField<Spec, J0, 0, NB>::load(w, e, lo, s, ds, ends, dsize);
     if (!WideField<Spec, J0, 0, NB>::nat(w, e, lo)) return false;
-    WideField<Spec, J0, 0, NB>::template store<ERR>(w, e, lo, to_stream, fs, r, errs);
+    WideField<Spec, J0, 0, NB>::template store<ERR>(w, e, lo, to_stream, fs, r, m.errs);
     return true;
 }
+
+// ---- sparse records on the fast path (the PRESENT kernels, small tables) ------------------
+// A Writer that skipped some setters leaves a table of k <= N entries whose tags are a strictly
+// increasing subset of the schema's, so the reference's binary search finds exactly those tags
+// and the entry of the tag of rank j sits at index popcount(ranks present below j).
+
+// The tags of a schema's Writer table as a 256-bit set (tags <= 255), one word per 64 tags.
+template <class Spec>
+struct TagSet {
+    static constexpr uint64_t word(int w) {
+        uint64_t v = 0;
+        for (int k = 0; k < Spec::N; k++)
+            if ((int)(Spec::stag[k] >> 6) == w) v |= 1ull << (Spec::stag[k] & 63);
+        return v;
+    }
+};
+
+// The ranks (positions in the full Writer table) of the tags a small table at ts holds, nent <= N
+// entries; false unless they are strictly increasing and all the schema's.  One byte read per
+// entry (unrolled over N, entries past nent read entry 0 and count for nothing).
+template <class Spec>
+__device__ __forceinline__ bool present_ranks(const LdsSrc &s, int ts, uint32_t nent, uint32_t &ranks) {
+    constexpr int N = Spec::N;
+    static_assert(N <= 32 && !Spec::big, "rank masks of small tables only");
+    uint32_t tag[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) tag[j] = s.u8(ts + ((uint32_t)j < nent ? 3 * j : 0));
+    // the table's tags as a set, kept only for the words the schema has tags in (a tag in
+    // another word is foreign)
+    constexpr uint64_t set[4] = {TagSet<Spec>::word(0), TagSet<Spec>::word(1), TagSet<Spec>::word(2),
+                                 TagSet<Spec>::word(3)};
+    constexpr uint32_t words = (set[0] ? 1u : 0u) | (set[1] ? 2u : 0u) | (set[2] ? 4u : 0u) | (set[3] ? 8u : 0u);
+    uint64_t have[4] = {0, 0, 0, 0};
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const bool in = (uint32_t)j < nent;
+        if (j > 0) ok = ok & (!in | (tag[j] > tag[j - 1]));
+        ok = ok & (!in | (((words >> (tag[j] >> 6)) & 1u) != 0));
+        const uint64_t bit = in ? 1ull << (tag[j] & 63) : 0ull;
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+            if (set[w]) have[w] |= (words == (1u << w) || (tag[j] >> 6) == (uint32_t)w) ? bit : 0ull;
+    }
+#pragma unroll
+    for (int w = 0; w < 4; w++) ok = ok & ((have[w] & ~set[w]) == 0); // no foreign tag
+    ranks = 0;
+#pragma unroll
+    for (int k = 0; k < N; k++) ranks |= (uint32_t)((have[Spec::stag[k] >> 6] >> (Spec::stag[k] & 63)) & 1) << k;
+    return ok;
+}
+
+// Ranks [J0, J1) of a record whose table holds the ranks in `ranks`: each field's ONE entry read
+// from the slab at its popcount index (an absent field reads an entry or the trailer behind the
+// table and drops it), then window, type check, decode and store as wide_batch.
+template <class Spec, int J0, int J1, bool ERR>
+__device__ __forceinline__ bool present_batch(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint32_t ranks,
+                                              uint64_t r, const FieldSet &fs, long long to_stream, RecMasks &m) {
+    constexpr int NB = J1 - J0;
+    uint32_t ends[NB];
+#pragma unroll
+    for (int k = 0; k < NB; k++) {
+        const int p = ts + 3 * (int)__builtin_popcount(ranks & ((1u << (J0 + k)) - 1u));
+        const uint32_t end = (s.u8(p + 1) << 8) | s.u8(p + 2);
+        const bool has = ((ranks >> (J0 + k)) & 1) != 0;
+        ends[k] = has ? end : ~0u; // (~0 > dsize: absent to WideField::load as to m.field)
+        m.pres |= (has & (end <= dsize)) ? 1ull << Spec::order[J0 + k] : 0ull;
+    }
+    Win w[NB];
+    int e[NB], lo[NB];
+    WideField<Spec, J0, 0, NB>::load(w, e, lo, s, ds, ends, dsize);
+    if (!WideField<Spec, J0, 0, NB>::nat(w, e, lo)) return false;
+    WideField<Spec, J0, 0, NB>::template store<ERR>(w, e, lo, to_stream, fs, r, m.errs);
+    return true;
+}
+
+template <class Spec, int J0, int JE, bool ERR>
+struct PresentBatchesTo {
+    static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint32_t ranks,
+                                               uint64_t r, const FieldSet &fs, long long to_stream, RecMasks &m) {
+        if constexpr (J0 >= JE) {
+            return true;
+        } else {
+            constexpr int J1 = J0 + FAST_BATCH < JE ? J0 + FAST_BATCH : JE;
+            if (!present_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, ranks, r, fs, to_stream, m)) return false;
+            return PresentBatchesTo<Spec, J1, JE, ERR>::run(s, ts, ds, dsize, ranks, r, fs, to_stream, m);
+        }
+    }
+};
 
 template <class Spec, int J0, bool ERR>
 struct WideBatches {
     static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                               const FieldSet &fs, long long to_stream, uint64_t &errs) {
+                                               const FieldSet &fs, long long to_stream, RecMasks &m) {
         if constexpr (J0 >= Spec::N) {
             return true;
         } else {
             constexpr int J1 = J0 + FAST_BATCH < Spec::N ? J0 + FAST_BATCH : Spec::N;
-            if (!wide_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, r, fs, to_stream, errs)) return false;
-            return WideBatches<Spec, J1, ERR>::run(s, ts, ds, dsize, r, fs, to_stream, errs);
+            if (!wide_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, r, fs, to_stream, m)) return false;
+            return WideBatches<Spec, J1, ERR>::run(s, ts, ds, dsize, r, fs, to_stream, m);
         }
     }
 };
 
 // table entries [J0, JE) in batches of FAST_BATCH (a wave pair's half of a wide record)
-template <class Spec, int J0, int JE, bool ERR = false>
+template <class Spec, int J0, int JE, bool ERR = false, bool PRESENT = false>
 struct WideBatchesTo {
     static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                               const FieldSet &fs, long long to_stream, uint64_t &errs) {
+                                               const FieldSet &fs, long long to_stream, RecMasks &m) {
         if constexpr (J0 >= JE) {
             return true;
         } else {
             constexpr int J1 = J0 + FAST_BATCH < JE ? J0 + FAST_BATCH : JE;
-            if (!wide_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, r, fs, to_stream, errs)) return false;
-            return WideBatchesTo<Spec, J1, JE, ERR>::run(s, ts, ds, dsize, r, fs, to_stream, errs);
+            if (!wide_batch<Spec, J0, J1, ERR, PRESENT>(s, ts, ds, dsize, r, fs, to_stream, m)) return false;
+            return WideBatchesTo<Spec, J1, JE, ERR, PRESENT>::run(s, ts, ds, dsize, r, fs, to_stream, m);
         }
     }
 };
@@ -871,28 +977,62 @@ struct WideBatchesTo {
 template <class Spec, int P>
 __host__ __device__ constexpr int flat_part_lo(int h) {
     if (h >= P) return Spec::N;
-    if (P == 2) return h == 0 ? 0 : ((Spec::N / 2 + FAST_BATCH - 1) / FAST_BATCH) * FAST_BATCH;
+    // (at most N: for 2..7 fields the rounded-up boundary lay past the table, the generated source
+    // did not compile and the schema ran on the generic kernel; the first wave takes all of them)
+    if (P == 2) {
+        const int mid = ((Spec::N / 2 + FAST_BATCH - 1) / FAST_BATCH) * FAST_BATCH;
+        return h == 0 ? 0 : (mid < Spec::N ? mid : Spec::N);
+    }
     return (h * Spec::N) / P;
 }
-template <class Spec, bool ERR, int P, int H = 0>
+template <class Spec, bool ERR, int P, bool PRESENT = false, int H = 0>
 __device__ __forceinline__ bool wide_part_run(const LdsSrc &s, const Trailer &tr, uint64_t r, const FieldSet &fs,
-                                              long long to_stream, int h, uint64_t &errs) {
+                                              long long to_stream, int h, RecMasks &m) {
     if constexpr (H >= P) {
         return true;
     } else {
         constexpr int J0 = flat_part_lo<Spec, P>(H), J1 = flat_part_lo<Spec, P>(H + 1);
         if (h == H)
-            return WideBatchesTo<Spec, J0, J1, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs, to_stream, errs);
-        return wide_part_run<Spec, ERR, P, H + 1>(s, tr, r, fs, to_stream, h, errs);
+            return WideBatchesTo<Spec, J0, J1, ERR, PRESENT>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs,
+                                                                  to_stream, m);
+        return wide_part_run<Spec, ERR, P, PRESENT, H + 1>(s, tr, r, fs, to_stream, h, m);
     }
 }
-template <class Spec, bool ERR = false, int P = 2>
+template <class Spec, bool ERR = false, int P = 2, bool PRESENT = false>
 __device__ __forceinline__ bool fast_wide_half(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
-                                               long long to_stream, int h, uint64_t &errs) {
+                                               long long to_stream, int h, RecMasks &m) {
     if (re <= rs) return false;
     const Trailer tr = parse_trailer(s, rs, re);
     if ((tr.st != ST_OK) | (tr.big != Spec::big) | (tr.tsize != (Spec::big ? 6u : 3u) * (uint32_t)Spec::N)) return false;
-    return wide_part_run<Spec, ERR, P>(s, tr, r, fs, to_stream, h, errs);
+    return wide_part_run<Spec, ERR, P, PRESENT>(s, tr, r, fs, to_stream, h, m);
+}
+
+// The PRESENT kernels' part h of a record of a small-table schema of at most FAST_MAX_FIELDS
+// fields: any table of k <= N entries that present_ranks accepts (the full table included), the
+// ranks of this part through present_batch.  Every wave of the group reads the whole tag column
+// (it needs the ranks below its own part); m.pres gets this part's HasField bits.
+template <class Spec, bool ERR, int P, int H = 0>
+__device__ __forceinline__ bool present_part_run(const LdsSrc &s, const Trailer &tr, uint32_t ranks, uint64_t r,
+                                                 const FieldSet &fs, long long to_stream, int h, RecMasks &m) {
+    if constexpr (H >= P) {
+        return true;
+    } else {
+        constexpr int J0 = flat_part_lo<Spec, P>(H), J1 = flat_part_lo<Spec, P>(H + 1);
+        if (h == H)
+            return PresentBatchesTo<Spec, J0, J1, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, ranks, r, fs,
+                                                            to_stream, m);
+        return present_part_run<Spec, ERR, P, H + 1>(s, tr, ranks, r, fs, to_stream, h, m);
+    }
+}
+template <class Spec, bool ERR = false, int P = 2>
+__device__ __forceinline__ bool fast_present_half(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
+                                                  long long to_stream, int h, RecMasks &m) {
+    if (re <= rs) return false;
+    const Trailer tr = parse_trailer(s, rs, re);
+    if ((tr.st != ST_OK) | tr.big | (tr.tsize > 3u * (uint32_t)Spec::N)) return false;
+    uint32_t ranks;
+    if (!present_ranks<Spec>(s, (int)tr.tstart, tr.tsize / 3u, ranks)) return false;
+    return present_part_run<Spec, ERR, P>(s, tr, ranks, r, fs, to_stream, h, m);
 }
 
 // The whole record (columns, status, errmask); false: nothing final written, run the generic path.
@@ -902,11 +1042,11 @@ __device__ __forceinline__ bool fast_wide(const LdsSrc &s, int rs, int re, uint6
     if (re <= rs) return false;
     const Trailer tr = parse_trailer(s, rs, re);
     if ((tr.st != ST_OK) | (tr.big != Spec::big) | (tr.tsize != (Spec::big ? 6u : 3u) * (uint32_t)Spec::N)) return false;
-    uint64_t errs = 0;
-    if (!WideBatches<Spec, 0, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs, to_stream, errs))
+    RecMasks m;
+    if (!WideBatches<Spec, 0, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs, to_stream, m))
         return false;
     if (fs.status) fs.status[r] = ST_OK;
-    if constexpr (ERR) fs.errmask[r] = errs;
+    if constexpr (ERR) fs.errmask[r] = m.errs;
     return true;
 }
 
@@ -1027,9 +1167,11 @@ __device__ __forceinline__ Group make_group(const DecodeArgs &a, uint64_t base, 
 }
 
 // One group per wave: stage, decode, done.  ERR: the variant that also writes the per-record
-// field error masks (a.f.errmask, spec_decode_flat_errors).
-template <class Spec, bool ERR = false>
+// field error masks (a.f.errmask, spec_decode_flat_errors).  PRESENT (run-time schemas only): the
+// generic path with the HasField masks (a.f.present, spec_decode_flat_present).
+template <class Spec, bool ERR = false, bool PRESENT = false>
 __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
+    static_assert(!PRESENT || Spec::N == 0, "the schema-specialised PRESENT kernel is decode_flat_pair");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
@@ -1070,10 +1212,10 @@ __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
                 if (fast_wide<Spec, ERR>(s, rs, re, r, a.f, to_stream)) return;
             }
         }
-        decode_record_generic(s, rs, re, r, a.f, to_stream);
+        decode_record_generic<PRESENT>(s, rs, re, r, a.f, to_stream);
     } else if (valid) {
         GlobalSrc s{a.stream, a.stream_len};
-        decode_record_generic(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
+        decode_record_generic<PRESENT>(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
     }
 }
 
@@ -1084,7 +1226,11 @@ __device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
 // record (it rewrites every column).  Same LDS per 64 records, twice the waves: one wave's LDS
 // and memory latency overlaps the other's decode.  ERR: every wave's mask bits, OR-ed by wave 0.
 // P waves per group in general (P parts of the fields; jit.cpp FLAT_WAVES).
-template <class Spec, bool ERR = false, int P = 2>
+// PRESENT: also the HasField masks (a.f.present, spec_decode_flat_present), every wave's bits OR-ed
+// by wave 0 like the error bits.  A small-table schema of at most FAST_MAX_FIELDS fields takes
+// sparse records on the fast path (fast_present_half); the other schemas take full tables there
+// and send a subset table to the generic path.
+template <class Spec, bool ERR = false, int P = 2, bool PRESENT = false>
 __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = threadIdx.x >> 6;
@@ -1109,7 +1255,7 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     if (!cur.in_lds) {
         if (wave == 0 && valid) {
             GlobalSrc s{a.stream, a.stream_len};
-            decode_record_generic(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
+            decode_record_generic<PRESENT>(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
         }
         return;
     }
@@ -1118,28 +1264,37 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     LdsSrc s{(lds_u8 *)slab};
     const int rs = cur.rs(), re = cur.re();
     const long long to_stream = cur.to_stream();
-    uint64_t errs = 0;
-    const bool ok = valid && fast_wide_half<Spec, ERR, P>(s, rs, re, r, a.f, to_stream, wave, errs);
-    // waves 1 .. P-1: verdicts at slab + 256 (w - 1), ERR: mask bits after them (512 B per wave)
+    RecMasks mine;
+    bool ok;
+    if constexpr (PRESENT && Spec::N <= FAST_MAX_FIELDS && !Spec::big)
+        ok = valid && fast_present_half<Spec, ERR, P>(s, rs, re, r, a.f, to_stream, wave, mine);
+    else
+        ok = valid && fast_wide_half<Spec, ERR, P, PRESENT>(s, rs, re, r, a.f, to_stream, wave, mine);
+    // waves 1 .. P-1: verdicts at slab + 256 (w - 1), ERR: mask bits after them (512 B per wave),
+    // PRESENT: HasField bits after those (512 B per wave)
     uint64_t *xerr = (uint64_t *)(xch + 64 * (P - 1));
+    uint64_t *xpres = xerr + (ERR ? 64 * (P - 1) : 0);
     if (wave > 0) {
         xch[64 * (wave - 1) + lane] = ok ? 1u : 0u;
-        if constexpr (ERR) xerr[64 * (wave - 1) + lane] = errs;
+        if constexpr (ERR) xerr[64 * (wave - 1) + lane] = mine.errs;
+        if constexpr (PRESENT) xpres[64 * (wave - 1) + lane] = mine.pres;
     }
     __syncthreads(); // the other waves' verdicts (and their column stores) are in
     if (wave == 0 && valid) {
         bool all = ok;
-        uint64_t m = errs;
+        uint64_t m = mine.errs, pm = mine.pres;
 #pragma unroll
         for (int w = 1; w < P; w++) {
             all = all && xch[64 * (w - 1) + lane] != 0;
             if constexpr (ERR) m |= xerr[64 * (w - 1) + lane];
+            if constexpr (PRESENT) pm |= xpres[64 * (w - 1) + lane];
         }
         if (all) {
             if (a.f.status) a.f.status[r] = ST_OK;
             if constexpr (ERR) a.f.errmask[r] = m;
+            if constexpr (PRESENT) a.f.present[r] = pm;
         } else {
-            decode_record_generic(s, rs, re, r, a.f, to_stream);
+            decode_record_generic<PRESENT>(s, rs, re, r, a.f, to_stream);
         }
     }
 }

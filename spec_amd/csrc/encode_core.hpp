@@ -21,6 +21,7 @@ struct EncFields {
     const uint8_t *heaps[SPEC_KFIELDS];
     uint64_t heap_lens[SPEC_KFIELDS];
     uint32_t table_big_forced; // 1 if any tag > 255 (IsBigMessage holds for every record)
+    static constexpr bool kWideFields = false;
 };
 
 // The field set of a schema with more than SPEC_KFIELDS fields: the same members as EncFields,
@@ -35,6 +36,20 @@ struct WideEncFields {
     const void *const *cols;
     const uint8_t *const *heaps;
     const uint64_t *heap_lens;
+    static constexpr bool kWideFields = true;
+};
+
+// A field set with a per-record presence mask (spec_encode_flat_present): record r writes exactly
+// the fields f whose bit is set, bit f & 63 of present[(f >> 6) * stride + r] (stride = the batch's
+// record count: one word per record for <= 64 fields, else word-major).
+template <class Base>
+struct PresentFields : Base {
+    const uint64_t *present;
+    uint64_t stride;
+    // (a lane past the batch's last record writes no field, so it reads no column either)
+    __device__ __forceinline__ uint64_t present_word(uint32_t c, uint64_t r) const {
+        return r < stride ? present[c * stride + r] : 0ull;
+    }
 };
 
 // Passed by value as the kernel argument (lives in the kernarg segment => scalar loads,
@@ -69,6 +84,26 @@ struct WideEncodeArgs {
     uint64_t *total;
     static constexpr bool kWide = true;
 };
+
+// EncodeArgs / WideEncodeArgs over a field set with a presence mask (the spec_encode_flat_present
+// kernels of encode_flat.hip): the same members, so the kernel bodies read either.
+template <class Fields>
+struct PresentEncodeArgsT {
+    uint64_t n;
+    PresentFields<Fields> f;
+    uint32_t check_heaps;
+    uint32_t frame_head;
+    uint8_t *out;
+    uint64_t out_cap;
+    uint64_t *ends;
+    uint64_t ends_base;
+    uint64_t *block_sums;
+    uint64_t nblocks;
+    uint64_t *total;
+    static constexpr bool kWide = Fields::kWideFields;
+};
+using PresentEncodeArgs = PresentEncodeArgsT<EncFields>;
+using WidePresentEncodeArgs = PresentEncodeArgsT<WideEncFields>;
 
 constexpr int ENC_BLOCK = 256;            // records per encode block (4 waves, one record per lane)
 constexpr int ENC_SLAB = 20 * 1024 - 128; // per-wave output staging (LDS)
@@ -127,6 +162,7 @@ __device__ __forceinline__ uint64_t field_size(const FS &a, uint32_t f, uint64_t
 struct RecSize {
     uint64_t total, data;
     bool big;
+    uint32_t nent; // PRES: the record's table entries (the fields it writes)
 };
 
 // lists(f, r) returns the encoded size of a K_LIST field (nested encode); flat schemas have none.
@@ -134,10 +170,35 @@ struct NoLists {
     __device__ __forceinline__ uint64_t operator()(uint32_t, uint64_t) const { return 0; }
 };
 
-template <class Lists = NoLists, class FS>
+// PRES (FS = PresentFields<...>): only the fields of the record's presence mask are written
+// (w.Field(tag).<Kind>(v) for exactly those, internal/tests/pkg1/object.go:85-167); an absent
+// field's column is not read, so its span is never checked; IsBigMessage is per record, over the
+// tags written.
+template <bool PRES = false, class Lists = NoLists, class FS>
 __device__ __forceinline__ RecSize record_size(const FS &a, uint64_t r, bool check_heaps, bool &err,
                                                const Lists &lists = Lists()) {
     uint64_t data = 0;
+    if constexpr (PRES) {
+        uint32_t nent = 0;
+        bool big = false; // a written tag > 255
+        uint64_t w = 0;
+        for (uint32_t f = 0; f < a.nfields; f++) {
+            if ((f & 63) == 0) w = a.present_word(f >> 6, r);
+            if (!((w >> (f & 63)) & 1)) continue;
+            nent++;
+            big |= a.tags[f] > 255;
+            data += field_size(a, f, r, check_heaps, err);
+        }
+        big = big || (nent > 0 && data > 65535); // IsBigMessage of this record (below)
+        const uint64_t tsize = (uint64_t)nent * (big ? 6 : 3);
+        if (data > MAX_SIZE) err = true;
+        RecSize s;
+        s.data = data;
+        s.big = big;
+        s.nent = nent;
+        s.total = data + tsize + vlen32((uint32_t)data) + vlen32((uint32_t)tsize) + 1;
+        return s;
+    }
     for (uint32_t f = 0; f < a.nfields; f++)
         data += a.kinds[f] == K_LIST ? lists(f, r) : field_size(a, f, r, check_heaps, err);
     // IsBigMessage (internal/format/msg.go:43-61): any tag > 255 or any end offset > 65535;
@@ -148,6 +209,7 @@ __device__ __forceinline__ RecSize record_size(const FS &a, uint64_t r, bool che
     RecSize s;
     s.data = data;
     s.big = big;
+    s.nent = 0;
     s.total = data + tsize + vlen32((uint32_t)data) + vlen32((uint32_t)tsize) + 1;
     return s;
 }
@@ -540,14 +602,42 @@ struct NoListEmit {
 
 // One message (internal/writer/writer.go:376-553): fields in write order, table entries at
 // their sorted positions, trailer.  Returns the end position.
-template <class Sink, class Pos, class Lists = NoListEmit, class FS, class Inv>
+// PRES: only the fields of the record's presence mask, the table holding those alone: the entry of
+// field f sits at the number of written fields before it in the Writer's table order.  Up to 64
+// fields that is one popcount of the record's mask in table order (bit inv_order[f] = present bit
+// f, built once per record); a wider schema counts the written fields of smaller table position
+// per field (nfields^2 / 2 scalar-loaded steps per record: 5 k for 100 fields).
+template <bool PRES = false, class Sink, class Pos, class Lists = NoListEmit, class FS, class Inv>
 __device__ __forceinline__ Pos emit_message(const FS &a, const Sink &k, Pos start, uint64_t r, const RecSize &rs,
                                             const Inv *inv_order, const Lists &lists = Lists()) {
     Emit<Sink, Pos> em(k, start);
     const Pos tstart = start + (Pos)rs.data;
     const uint32_t esize = rs.big ? 6 : 3;
     uint64_t end = 0;
+    uint64_t pw = 0, tmask = 0; // PRES: the present word of the fields at hand; the mask in table order
+    if constexpr (PRES && !FS::kWideFields) {
+        pw = a.present_word(0, r);
+        for (uint32_t f = 0; f < a.nfields; f++) tmask |= ((pw >> f) & 1) << inv_order[f];
+    }
     for (uint32_t f = 0; f < a.nfields; f++) {
+        [[maybe_unused]] uint32_t tpos = 0; // PRES: the field's table entry
+        if constexpr (PRES) {
+            tpos = inv_order[f];
+            if constexpr (FS::kWideFields) {
+                if ((f & 63) == 0) pw = a.present_word(f >> 6, r);
+                if (!((pw >> (f & 63)) & 1)) continue;
+                uint32_t before = 0;
+                uint64_t gw = 0;
+                for (uint32_t g = 0; g < a.nfields; g++) {
+                    if ((g & 63) == 0) gw = a.present_word(g >> 6, r);
+                    before += (uint32_t)((gw >> (g & 63)) & 1) & (uint32_t)(inv_order[g] < tpos);
+                }
+                tpos = before;
+            } else {
+                if (!((pw >> f) & 1)) continue;
+                tpos = (uint32_t)__builtin_popcountll(tmask & ((1ull << tpos) - 1));
+            }
+        }
         const uint8_t *col = (const uint8_t *)a.cols[f];
         uint32_t kind = a.kinds[f];
         switch (kind) {
@@ -599,7 +689,9 @@ __device__ __forceinline__ Pos emit_message(const FS &a, const Sink &k, Pos star
         }
         end = (uint64_t)(em.pos - start);
         // table entry for this field at its sorted position (encode/msg.go:58-72)
-        Pos p = tstart + (Pos)((uint32_t)inv_order[f] * esize);
+        Pos p;
+        if constexpr (PRES) p = tstart + (Pos)(tpos * esize);
+        else p = tstart + (Pos)((uint32_t)inv_order[f] * esize);
         uint32_t tag = a.tags[f];
         if (rs.big) {
             k.st1(p, tag >> 8);
@@ -616,9 +708,10 @@ __device__ __forceinline__ Pos emit_message(const FS &a, const Sink &k, Pos star
     }
     em.finish();
     // trailer: rvarint(dataSize) | rvarint(tableSize) | type (encode/msg.go:36-39)
-    Emit<Sink, Pos> tr(k, tstart + (Pos)((uint64_t)a.nfields * esize));
+    const uint32_t nent = PRES ? rs.nent : a.nfields; // table entries
+    Emit<Sink, Pos> tr(k, tstart + (Pos)((uint64_t)nent * esize));
     tr.rvarint((uint32_t)rs.data);
-    tr.rvarint((uint32_t)(a.nfields * esize));
+    tr.rvarint((uint32_t)(nent * esize));
     tr.put1(rs.big ? T_BIG_MESSAGE : T_MESSAGE);
     tr.finish();
     return tr.pos;
@@ -660,6 +753,32 @@ struct RuntimeEnc {
             hd.finish();
         }
         emit_message(f, k, p + (Pos)HEAD, r, rs, inv_order, lists);
+    }
+};
+
+// RuntimeEnc over a field set with a presence mask (PresentFields): the same bodies with PRES.
+struct RuntimePresentEnc {
+    struct Rec {};
+    template <class FS>
+    static __device__ __forceinline__ Rec load(const FS &, uint64_t) { return Rec{}; }
+    template <class FS>
+    static __device__ __forceinline__ void load_cols(const FS &, uint64_t, Rec &) {}
+    template <class FS>
+    static __device__ __forceinline__ void load_heaps(const FS &, Rec &) {}
+    template <class FS>
+    static __device__ __forceinline__ RecSize size(const FS &f, const Rec &, uint64_t r, bool check, bool &err) {
+        return record_size<true>(f, r, check, err);
+    }
+    template <int HEAD = 0, class Sink, class Pos, class FS, class Inv>
+    static __device__ __forceinline__ void emit(const FS &f, const Sink &k, Pos p, uint64_t r, const Rec &,
+                                                const RecSize &rs, const Inv *inv_order) {
+        if constexpr (HEAD != 0) {
+            static_assert(HEAD == 4, "the frame head is a u32");
+            Emit<Sink, Pos> hd(k, p);
+            hd.put4(bswap32((uint32_t)rs.total));
+            hd.finish();
+        }
+        emit_message<true>(f, k, p + (Pos)HEAD, r, rs, inv_order);
     }
 };
 

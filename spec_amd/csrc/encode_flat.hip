@@ -83,6 +83,80 @@ __global__ __launch_bounds__(ENC_BLOCK) void encode_wide_write_frames_kernel(Wid
     encode_write_body<RuntimeEnc, WideEncodeArgs, FRAME_HEAD>(a, smem);
 }
 
+// spec_encode_flat_present[_frames]: the same bodies over a field set with a per-record presence
+// mask (RuntimePresentEnc: only the fields of a record's mask are written), narrow and wide, plain
+// and framed.  The scans are the dense encoders' (scan_block_sums<0|4>).
+__global__ __launch_bounds__(ENC_BLOCK) void encode_present_size_kernel(PresentEncodeArgs a) {
+    encode_size_body<RuntimePresentEnc>(a);
+}
+
+__global__ __launch_bounds__(1024) void encode_present_scan_kernel(uint64_t *block_sums, uint64_t nblocks,
+                                                                    uint64_t *total) {
+    scan_block_sums(block_sums, nblocks, total);
+}
+
+__global__ __launch_bounds__(1024) void encode_present_scan_frames_kernel(uint64_t *block_sums, uint64_t nblocks,
+                                                                           uint64_t *total, uint64_t n) {
+    scan_block_sums<FRAME_HEAD>(block_sums, nblocks, total, n);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_present_write_kernel(PresentEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimePresentEnc>(a, smem);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_present_write_frames_kernel(PresentEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimePresentEnc, PresentEncodeArgs, FRAME_HEAD>(a, smem);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_wide_present_size_kernel(WidePresentEncodeArgs a) {
+    encode_size_body<RuntimePresentEnc>(a);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_wide_present_write_kernel(WidePresentEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimePresentEnc>(a, smem);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void encode_wide_present_write_frames_kernel(WidePresentEncodeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    encode_write_body<RuntimePresentEnc, WidePresentEncodeArgs, FRAME_HEAD>(a, smem);
+}
+
+template <class A, class SizeK>
+static int launch_present_size(const A &a, SizeK size_kernel, hipStream_t stream) {
+    if (a.nblocks) hipLaunchKernelGGL(size_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), 0, stream, a);
+    if (a.frame_head)
+        hipLaunchKernelGGL(encode_present_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a.block_sums, a.nblocks,
+                           a.total, a.n);
+    else
+        hipLaunchKernelGGL(encode_present_scan_kernel, dim3(1), dim3(1024), 0, stream, a.block_sums, a.nblocks, a.total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_encode_present_size(const PresentEncodeArgs &a, hipStream_t stream) {
+    return launch_present_size(a, encode_present_size_kernel, stream);
+}
+
+int launch_encode_wide_present_size(const WidePresentEncodeArgs &a, hipStream_t stream) {
+    return launch_present_size(a, encode_wide_present_size_kernel, stream);
+}
+
+int launch_encode_present_write(const PresentEncodeArgs &a, hipStream_t stream) {
+    if (!a.nblocks) return 0;
+    hipLaunchKernelGGL(a.frame_head ? encode_present_write_frames_kernel : encode_present_write_kernel,
+                       dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(), stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_encode_wide_present_write(const WidePresentEncodeArgs &a, hipStream_t stream) {
+    if (!a.nblocks) return 0;
+    hipLaunchKernelGGL(a.frame_head ? encode_wide_present_write_frames_kernel : encode_wide_present_write_kernel,
+                       dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), enc_write_lds_bytes(), stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_encode_wide_size(const WideEncodeArgs &a, hipStream_t stream) {
     if (a.nblocks) hipLaunchKernelGGL(encode_wide_size_kernel, dim3((unsigned)a.nblocks), dim3(ENC_BLOCK), 0, stream, a);
     if (a.frame_head) hipLaunchKernelGGL(encode_wide_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a);

@@ -44,7 +44,8 @@ namespace {
 #include "build/rtc_sources.inc"
 
 // The kernels of a generated module, by program (load() has their names)
-enum DecodeFn { DEC_PAIR, DEC_PAIR_ERR }; // the errmask variant: spec_decode_flat_errors
+// (the errmask variants: spec_decode_flat_errors; the present variants: spec_decode_flat_present)
+enum DecodeFn { DEC_PAIR, DEC_PAIR_ERR, DEC_PAIR_PRESENT, DEC_PAIR_PRESENT_ERR };
 enum EncodeFn { ENC_SIZE, ENC_WRITE, ENC_WRITE_FRAMES };
 enum NestedFn { NEST_PAIR, NEST_RANGES };
 enum NestedEncFn { NENC_SIZE, NENC_WRITE, NENC_WRITE_FRAMES, NENC_WRITE_PAIR, NENC_WRITE_PAIR_FRAMES };
@@ -173,7 +174,15 @@ std::string generate_decode(const spec_schema *s) {
       << "  spec::decode_flat_pair<GenSpec, false, " << P << ">(a);\n}\n"
       << "extern \"C\" __global__ __launch_bounds__(" << 64 * P << ") void spec_decode_flat" << w
       << "_err_pair_jit(spec::DecodeArgs a) {\n"
-      << "  spec::decode_flat_pair<GenSpec, true, " << P << ">(a);\n}\n";
+      << "  spec::decode_flat_pair<GenSpec, true, " << P << ">(a);\n}\n"
+      // spec_decode_flat_present: the HasField masks, further instantiations in the same module
+      // (the kernels above keep their code; build()'s precompile of a schema covers these)
+      << "extern \"C\" __global__ __launch_bounds__(" << 64 * P << ") void spec_decode_flat" << w
+      << "_present_pair_jit(spec::DecodeArgs a) {\n"
+      << "  spec::decode_flat_pair<GenSpec, false, " << P << ", true>(a);\n}\n"
+      << "extern \"C\" __global__ __launch_bounds__(" << 64 * P << ") void spec_decode_flat" << w
+      << "_present_err_pair_jit(spec::DecodeArgs a) {\n"
+      << "  spec::decode_flat_pair<GenSpec, true, " << P << ", true>(a);\n}\n";
     return o.str();
 }
 
@@ -442,9 +451,14 @@ bool get_kernels(Entry &e, std::initializer_list<Kernel> kernels) {
 bool load_kernels(Entry &e, Prog p) {
     switch (p) {
     case DECODE: // (a wide / big-table schema's kernels have names of their own: generate_decode)
-        return get_kernels(e, {{DEC_PAIR, "spec_decode_flat_pair_jit"}, {DEC_PAIR_ERR, "spec_decode_flat_err_pair_jit"}}) ||
+        return get_kernels(e, {{DEC_PAIR, "spec_decode_flat_pair_jit"},
+                               {DEC_PAIR_ERR, "spec_decode_flat_err_pair_jit"},
+                               {DEC_PAIR_PRESENT, "spec_decode_flat_present_pair_jit"},
+                               {DEC_PAIR_PRESENT_ERR, "spec_decode_flat_present_err_pair_jit"}}) ||
                get_kernels(e, {{DEC_PAIR, "spec_decode_flat_wide_pair_jit"},
-                               {DEC_PAIR_ERR, "spec_decode_flat_wide_err_pair_jit"}});
+                               {DEC_PAIR_ERR, "spec_decode_flat_wide_err_pair_jit"},
+                               {DEC_PAIR_PRESENT, "spec_decode_flat_wide_present_pair_jit"},
+                               {DEC_PAIR_PRESENT_ERR, "spec_decode_flat_wide_present_err_pair_jit"}});
     case ENCODE:
         return get_kernels(e, {{ENC_SIZE, "spec_encode_size_jit"},
                                {ENC_WRITE, "spec_encode_write_jit"},
@@ -1667,8 +1681,8 @@ int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, doubl
     const Entry *ent = lookup(schema, DECODE);
     if (!ent) return 0;
     if (a.n <= a.r0) return 1;
-    // a wave pair per 64 records, one slab per pair (+ 256 B exchange, + 512 B of masks), the
-    // groups in 8 equal XCD shares
+    // a wave pair per 64 records, one slab per pair (+ 256 B exchange, + 512 B per kind of mask),
+    // the groups in 8 equal XCD shares
     DecodeArgs args = a;
     args.slab = decode_slab_bytes(avg_record);
     args.xcd = 1;
@@ -1676,9 +1690,11 @@ int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, doubl
     size_t size = sizeof(args);
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
                      HIP_LAUNCH_PARAM_END};
-    hipError_t e = hipModuleLaunchKernel(ent->fn[a.f.errmask ? DEC_PAIR_ERR : DEC_PAIR], (unsigned)groups, 1, 1,
-                                         64 * FLAT_WAVES, 1, 1,
-                                         args.slab + (FLAT_WAVES - 1) * (a.f.errmask ? 768 : 256), stream, nullptr, extra);
+    const int fn = a.f.present ? (a.f.errmask ? DEC_PAIR_PRESENT_ERR : DEC_PAIR_PRESENT)
+                               : (a.f.errmask ? DEC_PAIR_ERR : DEC_PAIR);
+    const unsigned xch = 256 + (a.f.errmask ? 512 : 0) + (a.f.present ? 512 : 0);
+    hipError_t e = hipModuleLaunchKernel(ent->fn[fn], (unsigned)groups, 1, 1, 64 * FLAT_WAVES, 1, 1,
+                                         args.slab + (FLAT_WAVES - 1) * xch, stream, nullptr, extra);
     return e == hipSuccess ? 1 : -1;
 }
 

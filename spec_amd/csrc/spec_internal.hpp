@@ -87,6 +87,11 @@ int encode_flat_passes(const spec_schema *schema, const void *const *columns, co
 int launch_encode_write(const spec_schema *schema, const EncodeArgs &a, hipStream_t stream);
 int launch_encode_wide_size(const WideEncodeArgs &a, hipStream_t stream);
 int launch_encode_wide_write(const WideEncodeArgs &a, hipStream_t stream);
+// encode_flat.hip: spec_encode_flat_present's passes (size + scan; write), narrow and wide
+int launch_encode_present_size(const PresentEncodeArgs &a, hipStream_t stream);
+int launch_encode_present_write(const PresentEncodeArgs &a, hipStream_t stream);
+int launch_encode_wide_present_size(const WidePresentEncodeArgs &a, hipStream_t stream);
+int launch_encode_wide_present_write(const WidePresentEncodeArgs &a, hipStream_t stream);
 // jit.cpp: schema-specialised encode pass 1 (write=false) or 3; 1 launched, 0 use the
 // precompiled kernel, <0 HIP error.
 int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write, hipStream_t stream);

@@ -144,3 +144,36 @@ def decode_frames_errors(schema: Schema, frames: torch.Tensor, ends: torch.Tenso
     _lib.check(rc, "spec_decode_frames_errors")
     em = errmask.view(words, -1)
     return Columns(schema, cols, status), (em[0, :r1] if words == 1 else em[:, :r1])
+
+
+def decode_frames_present(schema: Schema, frames: torch.Tensor, ends: torch.Tensor, r0: int = 0, r1: int | None = None,
+                          *, errors: bool = False, cols=None, status=None, present=None, errmask=None,
+                          cuda_stream=None):
+    """spec_decode_frames_present: decode_frames plus the HasField masks of decode_flat_present ->
+    (Columns, present[, errmask]), the masks int64 [r1] (more than 64 fields: [ceil(nfields / 64), r1]).
+    Records below r0 keep the masks they came with (zero when allocated here)."""
+    _check_dev(frames, "frames", torch.uint8)
+    _check_dev(ends, "ends", torch.int64)
+    n = ends.numel()
+    r1 = n if r1 is None else r1
+    if cols is None:
+        cols = alloc_columns(schema, n, frames.device)
+    if status is None:
+        status = torch.empty(n, dtype=torch.uint8, device=frames.device)
+    words = max(1, (len(schema) + 63) // 64)
+    if present is None:
+        present = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
+    if errors and errmask is None:
+        errmask = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
+    ptrs = (C.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
+    rc = _lib.lib().spec_decode_frames_present(C.byref(schema.c), _ptr(frames), frames.numel(), _ptr(ends), r0, r1, 0,
+                                               ptrs, _ptr(status), _ptr(errmask if errors else None), _ptr(present),
+                                               _stream_handle(cuda_stream))
+    _lib.check(rc, "spec_decode_frames_present")
+
+    def view(m):
+        m = m.view(words, -1)
+        return m[0, :r1] if words == 1 else m[:, :r1]
+
+    out = (Columns(schema, cols, status), view(present))
+    return out + (view(errmask),) if errors else out
