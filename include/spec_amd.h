@@ -696,8 +696,11 @@ int spec_parse_batch(uint32_t root, const uint8_t *stream_bytes, uint64_t stream
  * schema-specialised decode kernel that spec_decode_flat uses when one exists — the
  * analogue of the reference's generated readers (internal/lang/generator/message.go:97-186).
  * Optional: spec_decode_flat compiles it on first use.  Returns 1 if a specialised kernel
- * is ready, 0 if the generic kernel will be used (schema without a fast path, JIT disabled
- * or unavailable), <0 on an invalid schema.  Results never differ between the two. */
+ * is ready and a batch of n records in stream_len bytes will run it, 0 if the generic kernel
+ * will be used (schema without a fast path, JIT disabled or unavailable, or a mean record of
+ * more than about 615 bytes: the specialised kernels parse a 64-record group from an LDS slab
+ * of at most 40 KiB, sized from stream_len / n), <0 on an invalid schema.  Results never differ
+ * between the two. */
 int spec_decode_flat_prepare(const spec_schema *schema, uint64_t stream_len, uint64_t n);
 /* spec_decode_flat_jit_compile: diagnostic — run only the hiprtc compile of that kernel
  * (no device needed); returns the code-object size, 0 if the schema has no fast path. */
@@ -707,6 +710,13 @@ long long spec_decode_flat_jit_compile(const spec_schema *schema, uint64_t strea
  * Write(), internal/lang/generator/message.go:319-439); code-object size, 0 if the schema
  * has none (list fields, more than 32 fields). */
 long long spec_encode_flat_jit_compile(const spec_schema *schema);
+/* spec_encode_flat_prepare: the encoders' twin of spec_decode_flat_prepare — compile (once per
+ * device and schema) and load the schema-specialised kernels spec_encode_flat_size /
+ * spec_encode_flat / spec_encode_flat_frames use when the schema has them.  Optional: the first
+ * encode does it otherwise.  Returns 1 if they are loaded and ready on the current device, 0 if
+ * the run-time kernels will be used (list fields, more than 32 fields, JIT disabled or
+ * unavailable), <0 on an invalid schema.  Results never differ between the two. */
+int spec_encode_flat_prepare(const spec_schema *schema);
 /* spec_set_jit: 0 forces the generic kernel (also: environment SPEC_AMD_JIT=0). */
 void spec_set_jit(int enabled);
 

@@ -137,6 +137,7 @@ def _declare(L):
     L.spec_parse_messages.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.spec_parse_batch.argtypes = [C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp]
     L.spec_decode_flat_prepare.argtypes = [C.POINTER(SpecSchema), C.c_uint64, C.c_uint64]
+    L.spec_encode_flat_prepare.argtypes = [C.POINTER(SpecSchema)]
     L.spec_set_jit.argtypes = [C.c_int]
     L.spec_set_jit.restype = None
     L.spec_decode_flat_jit_compile.argtypes = [C.POINTER(SpecSchema), C.c_uint64, C.c_uint64]

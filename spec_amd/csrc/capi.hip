@@ -604,6 +604,12 @@ int spec_decode_flat_prepare(const spec_schema *schema, uint64_t stream_len, uin
     return spec::jit_prepare_decode_flat(schema, (double)stream_len / (double)n);
 }
 
+int spec_encode_flat_prepare(const spec_schema *schema) {
+    int rc = check_schema(schema);
+    if (rc) return rc;
+    return spec::jit_prepare_encode_flat(schema);
+}
+
 void spec_set_jit(int enabled) { spec::jit_set_enabled(enabled); }
 
 long long spec_decode_flat_jit_compile(const spec_schema *schema, uint64_t stream_len, uint64_t n) {

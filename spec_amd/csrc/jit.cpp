@@ -1674,7 +1674,14 @@ long long jit_compile_only_encode(const spec_schema *schema) {
     return (long long)compile_code(schema, ENCODE).size();
 }
 
-int jit_prepare_decode_flat(const spec_schema *schema, double) { return lookup(schema, DECODE) ? 1 : 0; }
+// (the answer is jit_launch_decode_flat's for a batch of that mean record size: a batch whose
+// 64-record span has no LDS slab launches the generic kernel whatever the schema)
+int jit_prepare_decode_flat(const spec_schema *schema, double avg_record) {
+    if (decode_slab_bytes(avg_record) == 0) return 0;
+    return lookup(schema, DECODE) ? 1 : 0;
+}
+
+int jit_prepare_encode_flat(const spec_schema *schema) { return lookup(schema, ENCODE) ? 1 : 0; }
 
 int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, double avg_record, hipStream_t stream) {
     if (decode_slab_bytes(avg_record) == 0) return 0; // records too large for LDS: generic kernel

@@ -71,6 +71,7 @@ long long jit_compile_only_nested(const spec_nested_schema *schema);
 // should launch the generic kernel, <0 on a HIP error.
 int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, double avg_record, hipStream_t stream);
 int jit_prepare_decode_flat(const spec_schema *schema, double avg_record);
+int jit_prepare_encode_flat(const spec_schema *schema); // 1: jit_launch_encode will launch, 0: it will not
 void jit_set_enabled(int on);
 long long jit_compile_only(const spec_schema *schema, double avg_record);
 long long jit_compile_only_encode(const spec_schema *schema);

@@ -238,6 +238,47 @@ def bench_wide_schemas():
             "big16": Schema([(256 + 37 * i, kinds[i % 15]) for i in range(16)])}
 
 
+def shape_sweep_schemas():
+    """The GPU suite's flat schemas at the sizes where the schema-specialised kernels change shape
+    (tests/test_gpu_schema_shapes.py; build() precompiles their hiprtc modules).  name -> Schema.
+
+    n<N>[p]: N fields, tags 1..N, kinds cycling through the 15 flat kinds from (15 - N) mod 15 (a
+    schema of fewer than 15 fields ends on STRING/BYTES), p: write order permuted (fixed seed).
+      1, 2, 8, 9, 17, 18, 33, 34, 49, 63, 64   the decode wave pair's split (decode_core.hpp flat_part_lo)
+      24, 25                                    FAST_MAX_FIELDS: fast_present_half | fast_wide_half
+      21, 22, 32, 33                            SpecEnc: register-built table | emit_table; the last
+                                                specialised encoder | the run-time one
+    big21, big22: tags 250, 253, ... (a tag > 255: every table big; 6N = 126 | 132, a one- | two-byte
+    reverse varint).  tag255, tag256: tags (254, 255) | (255, 256), small | big tables.
+    tagwords8: tags in all four words of present_ranks' tag set.  tags3w: tags (1, 2, 200), a set
+    with two empty words (foreign tags there).  heap16: 6 string, 6 bytes and 4 integer fields."""
+    kinds = [Kind(k) for k in range(1, 16)]
+
+    def cyc(tags, perm_seed=None):
+        n = len(tags)
+        if perm_seed is not None:
+            tags = [int(t) for t in np.random.default_rng(perm_seed).permutation(tags)]
+        return Schema([(t, kinds[(15 - n % 15 + i) % 15]) for i, t in enumerate(tags)])
+
+    out = {}
+    permuted = {17, 21, 24, 34, 63}
+    for n in (1, 2, 8, 9, 17, 18, 21, 22, 24, 25, 32, 33, 34, 49, 63, 64):
+        p = n in permuted
+        out[f"n{n}{'p' if p else ''}"] = cyc(list(range(1, n + 1)), 100 + n if p else None)
+    out["big21"] = cyc([250 + 3 * i for i in range(21)])
+    out["big22"] = cyc([250 + 3 * i for i in range(22)])
+    out["tag255"] = cyc([254, 255])
+    out["tag256"] = cyc([255, 256])
+    words = [int(t) for t in np.random.default_rng(8).permutation([1, 63, 64, 127, 128, 191, 192, 255])]
+    out["tagwords8"] = Schema(list(zip(words, [Kind.INT32, Kind.STRING, Kind.UINT64, Kind.BYTES, Kind.BOOL,
+                                               Kind.FLOAT64, Kind.BIN128, Kind.INT16])))
+    out["tags3w"] = cyc([1, 2, 200])
+    S, B = Kind.STRING, Kind.BYTES
+    out["heap16"] = Schema(list(enumerate([S, B, Kind.INT32, S, B, S, B, Kind.UINT64, S, B, S, B, Kind.INT16, S, B,
+                                           Kind.INT64], start=1)))
+    return out
+
+
 # ---- byte streams for the LZ4 paths (tests/test_gpu_lz4_compress.py, tools/bench_lz4_compress.py) ----
 LZ4_KINDS = ("text", "random", "mixed", "zeros", "period3", "period200", "records", "chunks", "longlit")
 

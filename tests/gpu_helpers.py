@@ -13,6 +13,37 @@ def oracle_encode(schema, cols, heaps, n):
     return O.encode_flat_batch(schema.tags, schema.kinds, cols, [heaps.get(f) for f in range(len(schema))], n)
 
 
+SLAB_MAX_CHUNKS = 40  # decode_core.hpp: the 1 KiB chunks of the largest LDS slab of a 64-record group
+
+
+def slab_fits(stream_len: int, n: int) -> bool:
+    """decode_core.hpp decode_slab_bytes(stream_len / n) != 0: a batch of this mean record size (below
+    about 615 bytes) launches the schema's specialised decode kernels; a larger one launches the
+    generic kernel whatever the schema (jit.cpp jit_launch_decode_flat)."""
+    return n > 0 and int(stream_len / n * 64 * 1.04 / 1024.0) + 1 <= SLAB_MAX_CHUNKS
+
+
+def require_specialised(schema, name="", decode=None, encode=False):
+    """A "jit" leg proves itself: the schema-specialised (hiprtc) kernels of `schema` are compiled,
+    loaded and the ones the next launch takes.  Without this a module that fails to compile or load
+    prints one line to stderr, the generic kernel runs with the same results and the leg passes
+    having tested the generic kernel twice.  decode = (stream bytes, records) of the batch about to be
+    decoded: the launch also takes the generic kernel when the batch's mean record has no LDS slab,
+    and spec_decode_flat_prepare answers for that batch."""
+    import ctypes as C
+
+    L = spec_amd.lib()
+    what = name or f"schema of {len(schema)} fields, tags {schema.tags}"
+    if decode is not None:
+        stream_len, n = (int(x) for x in decode)
+        rc = L.spec_decode_flat_prepare(C.byref(schema.c), stream_len, n)
+        assert rc == 1, (f"{what}: the specialised decode kernels will not run on {n} records in {stream_len} bytes "
+                         f"(spec_decode_flat_prepare = {rc}, slab fits: {slab_fits(stream_len, n)})")
+    if encode:
+        rc = L.spec_encode_flat_prepare(C.byref(schema.c))
+        assert rc == 1, f"{what}: no specialised encode kernels (spec_encode_flat_prepare = {rc})"
+
+
 def to_dev(a: np.ndarray, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 

@@ -109,6 +109,31 @@ def test_argument_validation_without_gpu():
     assert L.spec_encode_flat_size(C.byref(s), cols, 1000, C.c_void_p(1), ws - 1, None, None) == -5
 
 
+def test_prepare_argument_validation_without_gpu():
+    """spec_decode_flat_prepare and its twin spec_encode_flat_prepare: an invalid schema is < 0 before
+    any HIP call; with the JIT off the answer is 0 (the generic / run-time kernels) without one."""
+    L = spec_amd.lib()
+    bad = _lib.SpecSchema()
+    bad.nfields = 1
+    bad.fields[0].tag = 1
+    bad.fields[0].kind = 42
+    over = _lib.SpecSchema()
+    over.nfields = _lib.SPEC_MAX_FIELDS + 1
+    assert L.spec_decode_flat_prepare(None, 1000, 10) == -1
+    assert L.spec_encode_flat_prepare(None) == -1
+    for s in (bad, over):
+        assert L.spec_decode_flat_prepare(C.byref(s), 1000, 10) == -1
+        assert L.spec_encode_flat_prepare(C.byref(s)) == -1
+    assert L.spec_decode_flat_prepare(C.byref(bad), 0, 0) == -1  # (checked before the n == 0 shortcut)
+    L.spec_set_jit(0)
+    try:
+        assert L.spec_decode_flat_prepare(C.byref(spec_amd.FLAT16.c), 1000, 10) == 0
+        assert L.spec_encode_flat_prepare(C.byref(spec_amd.FLAT16.c)) == 0
+        assert L.spec_decode_flat_prepare(C.byref(spec_amd.FLAT16.c), 0, 0) == 0
+    finally:
+        L.spec_set_jit(1)
+
+
 def test_encode_tree_requires_begin_columns_without_gpu():
     """spec_encode_tree: a list table's BEGIN column has owner rows + 1 entries, so it is required
     whenever the OWNER has rows, even when every list is empty (0 element rows); rejected before

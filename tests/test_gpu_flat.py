@@ -11,7 +11,7 @@ import pytest
 import spec_amd
 from oracle import oracle as O
 from spec_amd import Field, Kind, Schema, workload
-from tests.gpu_helpers import check_decode, check_encode, concat_records, oracle_encode
+from tests.gpu_helpers import check_decode, check_encode, concat_records, oracle_encode, require_specialised
 
 pytestmark = pytest.mark.gpu
 
@@ -51,11 +51,15 @@ def kernel(request):
 def test_flat16_decode_parity(dev, kernel, n):
     cols, heaps = workload.flat16(n, seed=n)
     stream, ends = oracle_encode(FLAT16, cols, heaps, n)
+    if kernel == "jit":
+        require_specialised(FLAT16, "flat16", decode=(stream.size, n))
     check_decode(dev, FLAT16, stream, ends, f"flat16 n={n}")
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4096 + 17])
 def test_flat16_encode_bitexact(dev, kernel, n):
+    if kernel == "jit":
+        require_specialised(FLAT16, "flat16", encode=True)
     cols, heaps = workload.flat16(n, seed=n + 1)
     check_encode(dev, FLAT16, cols, heaps, n, f"flat16 n={n}")
 

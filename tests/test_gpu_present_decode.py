@@ -14,7 +14,7 @@ import torch
 import spec_amd
 from oracle import oracle as O
 from spec_amd import FLAT16, NESTED, Kind, Schema, workload
-from tests.gpu_helpers import concat_records, to_dev
+from tests.gpu_helpers import concat_records, require_specialised, to_dev
 from tests.present_helpers import (PATTERNS, check_present, decode_present_abi, oracle_present, pack_mask, patterns,
                                    random_columns, write_sparse)
 from tests.test_gpu_flat import write_record
@@ -56,6 +56,8 @@ def test_patterns(dev, kernel, name, n):
     schema = JIT_SCHEMAS[name]
     for p in PATTERNS:
         recs, bits = sparse(schema, n, p, seed=n)
+        if kernel == "jit":
+            require_specialised(schema, name, decode=(sum(len(r) for r in recs), n))
         want = check_present(dev, schema, recs, f"{name} {p} n={n} {kernel}", errors=p.startswith("half"))
         # a Writer's record has exactly the fields it wrote
         assert np.array_equal(want, pack_mask(bits))
