@@ -28,19 +28,7 @@ int kind_width(int kind) {
     return 0;
 }
 
-// Table order a Writer produces for this schema: messageStack.insert over the tags in write
-// order, insertion sort where an equal tag written later moves before the earlier one
-// (internal/writer/stack_msg.go:37-61).  order[j] = schema index of the j-th table entry.
-// The insertion moves a new entry left past every entry whose tag is >= its own, so the result
-// is the unique order by (tag ascending, write index descending): sorted in O(n log n) here
-// (a 1024-field schema in reverse tag order cost ~0.5 M swaps per call as an insertion sort).
-template <class T>
-void table_order(const spec_schema *s, T *order) {
-    uint32_t key[SPEC_MAX_FIELDS]; // tag << 16 | (0xffff - index): ascending = the Writer's order
-    for (uint32_t f = 0; f < s->nfields; f++) key[f] = (uint32_t)s->fields[f].tag << 16 | (0xffffu - f);
-    std::sort(key, key + s->nfields);
-    for (uint32_t j = 0; j < s->nfields; j++) order[j] = (T)(0xffffu - (key[j] & 0xffffu));
-}
+using spec::table_order; // spec_internal.hpp
 
 int check_schema(const spec_schema *s) {
     if (!s || s->nfields > SPEC_MAX_FIELDS) return SPEC_E_INVALID_ARGUMENT;
@@ -182,12 +170,19 @@ void fill_enc_fields(spec::EncFields &e, const spec_schema *schema, const void *
     table_order(schema, e.order);
 }
 
-template <class A>
-void fill_encode_args(A &a, const spec_schema *schema, const void *const *columns, uint64_t n) {
-    memset(&a, 0, sizeof(a));
-    a.n = n;
-    fill_enc_fields(a.f, schema, columns);
-    a.nblocks = (n + spec::ENC_BLOCK - 1) / spec::ENC_BLOCK;
+// The heaps of a call's string/bytes fields, checked and attached to a field set: dst_heaps[f] and
+// dst_lens[f] of an EncFields, or of a wide field set's staging copy.
+int attach_heaps(const spec_schema *s, const uint8_t *const *heaps, const uint64_t *lens, const uint8_t **dst_heaps,
+                 uint64_t *dst_lens) {
+    for (uint32_t f = 0; f < s->nfields; f++) {
+        const int k = s->fields[f].kind;
+        if (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) {
+            if (!heaps || !lens || (!heaps[f] && lens[f])) return SPEC_E_INVALID_ARGUMENT;
+            dst_heaps[f] = heaps[f];
+            dst_lens[f] = lens[f];
+        }
+    }
+    return SPEC_OK;
 }
 
 // Encode workspace: the block sums (nblocks + 1 words), then room for a wide schema's field set.
@@ -197,67 +192,106 @@ size_t enc_ws_sums(uint64_t n) {
     return (size_t)(((nblocks + 1) * sizeof(uint64_t) + 255) & ~(uint64_t)255);
 }
 
-// A schema with more than SPEC_KFIELDS fields: its field set (tags, kinds, table positions,
-// columns, heaps) written into the workspace after the block sums, from a pinned slot on the
-// call's stream; the kernel argument holds the pointers.
+// One call of the flat encoder, as its C ABI entry point checked it.
+struct FlatEncodeCall {
+    const spec_schema *schema;
+    const void *const *columns;
+    const uint8_t *const *heaps;
+    const uint64_t *heap_lens;
+    const uint64_t *present; // the presence masks (spec_encode_flat_present*), else unused
+    uint64_t n;
+    uint32_t check_heaps;    // 0: sizes only, no heaps attached (spec_encode_flat_size)
+    uint32_t frame_head;
+    uint8_t *out;
+    uint64_t out_cap;
+    uint64_t *ends;
+    uint64_t ends_base;
+    void *workspace;
+    uint64_t *total;
+    int passes;
+    hipStream_t stream;
+};
+
+// The call's field set into the argument block.  A schema with more than SPEC_KFIELDS fields
+// (A::kWide): its field set (tags, kinds, table positions, columns, heaps) written into the
+// workspace after the block sums, from a pinned slot on the call's stream; the kernel argument
+// holds the pointers.
 template <class A>
-int fill_wide_encode_args(A &a, const spec_schema *schema, const void *const *columns,
-                          const uint8_t *const *heaps, const uint64_t *heap_lens, uint64_t n, void *workspace,
-                          hipStream_t st) {
+int fill_encode_args(A &a, const FlatEncodeCall &c) {
+    const spec_schema *schema = c.schema;
     memset(&a, 0, sizeof(a));
-    const uint32_t N = schema->nfields;
-    a.n = n;
-    a.nblocks = (n + spec::ENC_BLOCK - 1) / spec::ENC_BLOCK;
-    uint8_t *dev = (uint8_t *)workspace + enc_ws_sums(n);
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_tags = 0, o_kinds = al(o_tags + 2 * N), o_inv = al(o_kinds + N), o_cols = al(o_inv + 2 * N),
-                 o_heaps = o_cols + 8 * N, o_lens = o_heaps + 8 * N, bytes = o_lens + 8 * N;
-    if (bytes > WIDE_FIELDS_BYTES) return SPEC_E_INVALID_ARGUMENT;
-    std::vector<uint8_t> h(bytes, 0);
-    uint16_t order[SPEC_MAX_FIELDS];
-    table_order(schema, order);
-    for (uint32_t f = 0; f < N; f++) {
-        ((uint16_t *)(h.data() + o_tags))[f] = schema->fields[f].tag;
-        h[o_kinds + f] = schema->fields[f].kind;
-        ((uint16_t *)(h.data() + o_inv))[order[f]] = (uint16_t)f;
-        ((const void **)(h.data() + o_cols))[f] = columns ? columns[f] : nullptr;
-        const int k = schema->fields[f].kind;
-        if (heaps && heap_lens && (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES)) {
-            if (!heaps[f] && heap_lens[f]) return SPEC_E_INVALID_ARGUMENT;
-            ((const uint8_t **)(h.data() + o_heaps))[f] = heaps[f];
-            ((uint64_t *)(h.data() + o_lens))[f] = heap_lens[f];
+    a.n = c.n;
+    a.nblocks = (c.n + spec::ENC_BLOCK - 1) / spec::ENC_BLOCK;
+    if constexpr (!A::kWide) {
+        fill_enc_fields(a.f, schema, c.columns);
+        return c.check_heaps ? attach_heaps(schema, c.heaps, c.heap_lens, a.f.heaps, a.f.heap_lens) : SPEC_OK;
+    } else {
+        const uint32_t N = schema->nfields;
+        uint8_t *dev = (uint8_t *)c.workspace + enc_ws_sums(c.n);
+        auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        const size_t o_tags = 0, o_kinds = al(o_tags + 2 * N), o_inv = al(o_kinds + N), o_cols = al(o_inv + 2 * N),
+                     o_heaps = o_cols + 8 * N, o_lens = o_heaps + 8 * N, bytes = o_lens + 8 * N;
+        if (bytes > WIDE_FIELDS_BYTES) return SPEC_E_INVALID_ARGUMENT;
+        std::vector<uint8_t> h(bytes, 0);
+        uint16_t order[SPEC_MAX_FIELDS];
+        table_order(schema, order);
+        for (uint32_t f = 0; f < N; f++) {
+            ((uint16_t *)(h.data() + o_tags))[f] = schema->fields[f].tag;
+            h[o_kinds + f] = schema->fields[f].kind;
+            ((uint16_t *)(h.data() + o_inv))[order[f]] = (uint16_t)f;
+            ((const void **)(h.data() + o_cols))[f] = c.columns[f];
+            if (schema->fields[f].tag > 255) a.f.table_big_forced = 1;
         }
-        if (schema->fields[f].tag > 255) a.f.table_big_forced = 1;
+        if (c.check_heaps) {
+            const int rc = attach_heaps(schema, c.heaps, c.heap_lens, (const uint8_t **)(h.data() + o_heaps),
+                                        (uint64_t *)(h.data() + o_lens));
+            if (rc) return rc;
+        }
+        a.f.nfields = N;
+        a.f.tags = (const uint16_t *)(dev + o_tags);
+        a.f.kinds = dev + o_kinds;
+        a.f.inv_order = (const uint16_t *)(dev + o_inv);
+        a.f.cols = (const void *const *)(dev + o_cols);
+        a.f.heaps = (const uint8_t *const *)(dev + o_heaps);
+        a.f.heap_lens = (const uint64_t *)(dev + o_lens);
+        const hipError_t e = upload_async(dev, h.data(), bytes, c.stream);
+        return e == hipSuccess ? SPEC_OK : hip_rc(e);
     }
-    a.f.nfields = N;
-    a.f.tags = (const uint16_t *)(dev + o_tags);
-    a.f.kinds = dev + o_kinds;
-    a.f.inv_order = (const uint16_t *)(dev + o_inv);
-    a.f.cols = (const void *const *)(dev + o_cols);
-    a.f.heaps = (const uint8_t *const *)(dev + o_heaps);
-    a.f.heap_lens = (const uint64_t *)(dev + o_lens);
-    const hipError_t e = upload_async(dev, h.data(), bytes, st);
-    return e == hipSuccess ? SPEC_OK : hip_rc(e);
 }
 
-// spec_encode_flat_present (frame_head 0) and spec_encode_flat_present_frames (4): the run-time
-// encoder's passes over a field set with the per-record presence masks; out == NULL sizes only
+// The requested passes over a filled argument block.
 template <class A>
-int encode_present_launch(A &a, const uint64_t *present, uint64_t n, uint8_t *out, uint64_t out_cap,
-                                 uint64_t *ends, void *workspace, uint64_t *total, hipStream_t st, uint32_t frame_head,
-                                 int (*size)(const A &, hipStream_t), int (*write)(const A &, hipStream_t)) {
-    a.f.present = present;
-    a.f.stride = n;
-    a.check_heaps = 1;
-    a.frame_head = frame_head;
-    a.out = out;
-    a.out_cap = out ? out_cap : 0;
-    a.ends = ends;
-    a.block_sums = (uint64_t *)workspace;
-    a.total = total;
-    if (size(a, st)) return hip_rc(hipGetLastError());
-    if (out && write(a, st)) return hip_rc(hipGetLastError());
+int run_encode_passes(A &a, const FlatEncodeCall &c) {
+    if constexpr (A::kPresent) {
+        a.f.present = c.present;
+        a.f.stride = c.n;
+    }
+    a.check_heaps = c.check_heaps;
+    a.frame_head = c.frame_head;
+    a.out = c.out;
+    a.out_cap = c.out_cap;
+    a.ends = c.ends;
+    a.ends_base = c.ends_base;
+    a.block_sums = (uint64_t *)c.workspace;
+    a.total = c.total;
+    if ((c.passes & spec::ENC_PASS_SIZE) && spec::launch_encode_size(c.schema, a, c.stream))
+        return hip_rc(hipGetLastError());
+    if ((c.passes & spec::ENC_PASS_WRITE) && spec::launch_encode_write(c.schema, a, c.stream))
+        return hip_rc(hipGetLastError());
     return SPEC_OK;
+}
+
+// Every flat encode call after its argument checks: the argument block of the schema's width
+// (Narrow or Wide: the one place a call chooses), filled and run.
+template <class Narrow, class Wide>
+int encode_flat_call(const FlatEncodeCall &c) {
+    int rc;
+    if (c.schema->nfields > SPEC_KFIELDS) {
+        Wide w;
+        return (rc = fill_encode_args(w, c)) ? rc : run_encode_passes(w, c);
+    }
+    Narrow a;
+    return (rc = fill_encode_args(a, c)) ? rc : run_encode_passes(a, c);
 }
 
 } // namespace
@@ -275,46 +309,9 @@ int encode_flat_passes(const spec_schema *schema, const void *const *columns, co
     if (rc) return rc;
     if (!columns || !workspace || (n && (!ends || !out))) return SPEC_E_INVALID_ARGUMENT;
     if (workspace_size < spec_encode_flat_workspace_size(n)) return SPEC_E_WORKSPACE;
-    if (schema->nfields > SPEC_KFIELDS) {
-        for (uint32_t f = 0; f < schema->nfields; f++) {
-            const int k = schema->fields[f].kind;
-            if ((k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) && (!heaps || !heap_lens)) return SPEC_E_INVALID_ARGUMENT;
-        }
-        WideEncodeArgs w{};
-        if ((rc = fill_wide_encode_args(w, schema, columns, heaps, heap_lens, n, workspace, stream))) return rc;
-        w.check_heaps = 1;
-        w.frame_head = frame_head;
-        w.out = out;
-        w.out_cap = out_cap;
-        w.ends = ends;
-        w.ends_base = ends_base;
-        w.block_sums = (uint64_t *)workspace;
-        w.total = total;
-        if ((passes & ENC_PASS_SIZE) && launch_encode_wide_size(w, stream)) return hip_rc(hipGetLastError());
-        if ((passes & ENC_PASS_WRITE) && launch_encode_wide_write(w, stream)) return hip_rc(hipGetLastError());
-        return SPEC_OK;
-    }
-    EncodeArgs a{};
-    fill_encode_args(a, schema, columns, n);
-    for (uint32_t f = 0; f < schema->nfields; f++) {
-        int k = schema->fields[f].kind;
-        if (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) {
-            if (!heaps || !heap_lens || (!heaps[f] && heap_lens[f])) return SPEC_E_INVALID_ARGUMENT;
-            a.f.heaps[f] = heaps[f];
-            a.f.heap_lens[f] = heap_lens[f];
-        }
-    }
-    a.check_heaps = 1;
-    a.frame_head = frame_head;
-    a.out = out;
-    a.out_cap = out_cap;
-    a.ends = ends;
-    a.ends_base = ends_base;
-    a.block_sums = (uint64_t *)workspace;
-    a.total = total;
-    if ((passes & ENC_PASS_SIZE) && launch_encode_size(schema, a, stream)) return hip_rc(hipGetLastError());
-    if ((passes & ENC_PASS_WRITE) && launch_encode_write(schema, a, stream)) return hip_rc(hipGetLastError());
-    return SPEC_OK;
+    return encode_flat_call<EncodeArgs, WideEncodeArgs>({schema, columns, heaps, heap_lens, nullptr, n, 1, frame_head,
+                                                         out, out_cap, ends, ends_base, workspace, total, passes,
+                                                         stream});
 }
 } // namespace spec
 
@@ -826,18 +823,6 @@ size_t spec_encode_nested_workspace_size_items(uint64_t n, uint64_t nitems) {
     return nested_ws_base(n) + (((size_t)nitems * 4 + 255) & ~(size_t)255) + (size_t)((n + 63) / 64);
 }
 
-static int heaps_of(spec::EncFields &e, const spec_schema *s, const uint8_t *const *heaps, const uint64_t *lens) {
-    for (uint32_t f = 0; f < s->nfields; f++) {
-        int k = s->fields[f].kind;
-        if (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) {
-            if (!heaps || !lens || (!heaps[f] && lens[f])) return SPEC_E_INVALID_ARGUMENT;
-            e.heaps[f] = heaps[f];
-            e.heap_lens[f] = lens[f];
-        }
-    }
-    return SPEC_OK;
-}
-
 // A nested schema with a half of more than SPEC_KFIELDS fields, encoded by the schema-tree
 // encoder (spec_encode_tree): the records' message with the list field as a LIST of MESSAGE
 // items — the same Writer calls (writer_list_msg.go:8-47), so the same bytes.  The list is always
@@ -944,8 +929,8 @@ static int encode_nested_impl(const spec_nested_schema *schema, const void *cons
     for (uint32_t f = 0; f < schema->outer.nfields; f++)
         if (f != list_f && !outer_columns[f]) return SPEC_E_INVALID_ARGUMENT;
     a.outer.cols[list_f] = nullptr;
-    if ((rc = heaps_of(a.outer, &schema->outer, outer_heaps, outer_heap_lens))) return rc;
-    if ((rc = heaps_of(a.item, &schema->item, item_heaps, item_heap_lens))) return rc;
+    if ((rc = attach_heaps(&schema->outer, outer_heaps, outer_heap_lens, a.outer.heaps, a.outer.heap_lens))) return rc;
+    if ((rc = attach_heaps(&schema->item, item_heaps, item_heap_lens, a.item.heaps, a.item.heap_lens))) return rc;
     a.item_begin = item_begin;
     a.nitems = nitems;
     a.check_heaps = 1;
@@ -989,7 +974,8 @@ int spec_encode_nested_frames(const spec_nested_schema *schema, const void *cons
 
 size_t spec_encode_flat_workspace_size(uint64_t n) { return enc_ws_sums(n) + WIDE_FIELDS_BYTES; }
 
-// spec_encode_flat_present[_frames]: argument checks, then encode_present_launch
+// spec_encode_flat_present (frame_head 0) and spec_encode_flat_present_frames (4): the run-time
+// encoder's passes over a field set with the per-record presence masks; out == NULL sizes only
 static int encode_flat_present_impl(const spec_schema *schema, const void *const *columns, const uint8_t *const *heaps,
                                     const uint64_t *heap_lens, const uint64_t *present, uint64_t n, uint8_t *out,
                                     uint64_t out_cap, uint64_t *ends, void *workspace, size_t workspace_size,
@@ -999,30 +985,9 @@ static int encode_flat_present_impl(const spec_schema *schema, const void *const
     if (schema->nfields == 0 || !present || !columns || !workspace || !total || (n && out && !ends))
         return SPEC_E_INVALID_ARGUMENT;
     if (workspace_size < spec_encode_flat_workspace_size(n)) return SPEC_E_WORKSPACE;
-    for (uint32_t f = 0; f < schema->nfields; f++) {
-        const int k = schema->fields[f].kind;
-        if ((k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) && (!heaps || !heap_lens || (!heaps[f] && heap_lens[f])))
-            return SPEC_E_INVALID_ARGUMENT;
-    }
-    if (schema->nfields > SPEC_KFIELDS) {
-        spec::WidePresentEncodeArgs w{};
-        if ((rc = fill_wide_encode_args(w, schema, columns, heaps, heap_lens, n, workspace, (hipStream_t)stream)))
-            return rc;
-        return encode_present_launch(w, present, n, out, out_cap, ends, workspace, total, (hipStream_t)stream,
-                                     frame_head, spec::launch_encode_wide_present_size,
-                                     spec::launch_encode_wide_present_write);
-    }
-    spec::PresentEncodeArgs a{};
-    fill_encode_args(a, schema, columns, n);
-    for (uint32_t f = 0; f < schema->nfields; f++) {
-        const int k = schema->fields[f].kind;
-        if (k == SPEC_KIND_STRING || k == SPEC_KIND_BYTES) {
-            a.f.heaps[f] = heaps[f];
-            a.f.heap_lens[f] = heap_lens[f];
-        }
-    }
-    return encode_present_launch(a, present, n, out, out_cap, ends, workspace, total, (hipStream_t)stream, frame_head,
-                                 spec::launch_encode_present_size, spec::launch_encode_present_write);
+    return encode_flat_call<spec::PresentEncodeArgs, spec::WidePresentEncodeArgs>(
+        {schema, columns, heaps, heap_lens, present, n, 1, frame_head, out, out ? out_cap : 0, ends, 0, workspace, total,
+         spec::ENC_PASS_SIZE | (out ? spec::ENC_PASS_WRITE : 0), (hipStream_t)stream});
 }
 
 int spec_encode_flat_present(const spec_schema *schema, const void *const *columns, const uint8_t *const *heaps,
@@ -1047,21 +1012,9 @@ int spec_encode_flat_size(const spec_schema *schema, const void *const *columns,
     if (rc) return rc;
     if (!columns || !workspace) return SPEC_E_INVALID_ARGUMENT;
     if (workspace_size < spec_encode_flat_workspace_size(n)) return SPEC_E_WORKSPACE;
-    if (schema->nfields > SPEC_KFIELDS) {
-        spec::WideEncodeArgs w{};
-        if ((rc = fill_wide_encode_args(w, schema, columns, nullptr, nullptr, n, workspace, (hipStream_t)stream)))
-            return rc;
-        w.block_sums = (uint64_t *)workspace;
-        w.total = total;
-        if (spec::launch_encode_wide_size(w, (hipStream_t)stream)) return hip_rc(hipGetLastError());
-        return SPEC_OK;
-    }
-    spec::EncodeArgs a{};
-    fill_encode_args(a, schema, columns, n);
-    a.block_sums = (uint64_t *)workspace;
-    a.total = total;
-    if (spec::launch_encode_size(schema, a, (hipStream_t)stream)) return hip_rc(hipGetLastError());
-    return SPEC_OK;
+    return encode_flat_call<spec::EncodeArgs, spec::WideEncodeArgs>({schema, columns, nullptr, nullptr, nullptr, n, 0, 0,
+                                                                     nullptr, 0, nullptr, 0, workspace, total,
+                                                                     spec::ENC_PASS_SIZE, (hipStream_t)stream});
 }
 
 int spec_encode_flat(const spec_schema *schema, const void *const *columns,

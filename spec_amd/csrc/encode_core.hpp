@@ -22,6 +22,7 @@ struct EncFields {
     uint64_t heap_lens[SPEC_KFIELDS];
     uint32_t table_big_forced; // 1 if any tag > 255 (IsBigMessage holds for every record)
     static constexpr bool kWideFields = false;
+    static constexpr bool kPresent = false;
 };
 
 // The field set of a schema with more than SPEC_KFIELDS fields: the same members as EncFields,
@@ -37,6 +38,7 @@ struct WideEncFields {
     const uint8_t *const *heaps;
     const uint64_t *heap_lens;
     static constexpr bool kWideFields = true;
+    static constexpr bool kPresent = false;
 };
 
 // A field set with a per-record presence mask (spec_encode_flat_present): record r writes exactly
@@ -46,6 +48,7 @@ template <class Base>
 struct PresentFields : Base {
     const uint64_t *present;
     uint64_t stride;
+    static constexpr bool kPresent = true;
     // (a lane past the batch's last record writes no field, so it reads no column either)
     __device__ __forceinline__ uint64_t present_word(uint32_t c, uint64_t r) const {
         return r < stride ? present[c * stride + r] : 0ull;
@@ -53,10 +56,13 @@ struct PresentFields : Base {
 };
 
 // Passed by value as the kernel argument (lives in the kernarg segment => scalar loads,
-// the per-field loop branches are wave-uniform).
-struct EncodeArgs {
+// the per-field loop branches are wave-uniform).  One block for every flat encoder: Fields is the
+// schema in the argument itself (EncFields) or in device memory (WideEncFields: more than
+// SPEC_KFIELDS fields), dense or behind a presence mask (PresentFields<...>).
+template <class Fields>
+struct EncodeArgsT {
     uint64_t n;
-    EncFields f;
+    Fields f;
     uint32_t check_heaps;  // 1 when heaps/heap_lens are known (full encode, not size-only)
     uint32_t frame_head;   // 0, or 4: every record behind its mpx frame head (selects the framed kernels)
     uint8_t *out;
@@ -66,44 +72,13 @@ struct EncodeArgs {
     uint64_t *block_sums;  // workspace: per-block encoded bytes, then exclusive offsets
     uint64_t nblocks;
     uint64_t *total;
-    static constexpr bool kWide = false;
-};
-
-// EncodeArgs of a schema with more than SPEC_KFIELDS fields (encode_flat.hip wide kernels).
-struct WideEncodeArgs {
-    uint64_t n;
-    WideEncFields f;
-    uint32_t check_heaps;
-    uint32_t frame_head;
-    uint8_t *out;
-    uint64_t out_cap;
-    uint64_t *ends;
-    uint64_t ends_base;
-    uint64_t *block_sums;
-    uint64_t nblocks;
-    uint64_t *total;
-    static constexpr bool kWide = true;
-};
-
-// EncodeArgs / WideEncodeArgs over a field set with a presence mask (the spec_encode_flat_present
-// kernels of encode_flat.hip): the same members, so the kernel bodies read either.
-template <class Fields>
-struct PresentEncodeArgsT {
-    uint64_t n;
-    PresentFields<Fields> f;
-    uint32_t check_heaps;
-    uint32_t frame_head;
-    uint8_t *out;
-    uint64_t out_cap;
-    uint64_t *ends;
-    uint64_t ends_base;
-    uint64_t *block_sums;
-    uint64_t nblocks;
-    uint64_t *total;
     static constexpr bool kWide = Fields::kWideFields;
+    static constexpr bool kPresent = Fields::kPresent;
 };
-using PresentEncodeArgs = PresentEncodeArgsT<EncFields>;
-using WidePresentEncodeArgs = PresentEncodeArgsT<WideEncFields>;
+using EncodeArgs = EncodeArgsT<EncFields>;
+using WideEncodeArgs = EncodeArgsT<WideEncFields>;
+using PresentEncodeArgs = EncodeArgsT<PresentFields<EncFields>>;
+using WidePresentEncodeArgs = EncodeArgsT<PresentFields<WideEncFields>>;
 
 constexpr int ENC_BLOCK = 256;            // records per encode block (4 waves, one record per lane)
 constexpr int ENC_SLAB = 20 * 1024 - 128; // per-wave output staging (LDS)
@@ -724,10 +699,12 @@ __device__ __forceinline__ Pos emit_message(const FS &a, const Sink &k, Pos star
 //   P::load(a, r)                  (all loads of a lane issued together)
 //   P::size(a, rec, r, check, err) RecSize of the record
 //   P::emit(a, sink, pos, r, rec, rs, inv_order)   the record's bytes
-// RuntimeEnc reads the schema from the kernel arguments (one switch per field);
-// SpecEnc<Spec> has it as compile-time constants (jit.cpp).
+// RuntimeEncT<PRES> (RuntimeEnc = RuntimeEncT<false>) reads the schema from the kernel arguments
+// (one switch per field); SpecEnc<Spec> has it as compile-time constants (jit.cpp).
 
-struct RuntimeEnc {
+// PRES: over a field set with a presence mask (PresentFields), the same bodies with PRES.
+template <bool PRES>
+struct RuntimeEncT {
     struct Rec {};
     template <class FS>
     static __device__ __forceinline__ Rec load(const FS &, uint64_t) { return Rec{}; }
@@ -738,7 +715,7 @@ struct RuntimeEnc {
     template <class Lists = NoLists, class FS>
     static __device__ __forceinline__ RecSize size(const FS &f, const Rec &, uint64_t r, bool check, bool &err,
                                                    const Lists &lists = Lists()) {
-        return record_size(f, r, check, err, lists);
+        return record_size<PRES>(f, r, check, err, lists);
     }
     // HEAD = 4: the mpx frame head (u32 BE message size, mpx/conn_writer.go:84-97) at p, the
     // message behind it; its table and trailer are placed from the message's first byte
@@ -752,35 +729,10 @@ struct RuntimeEnc {
             hd.put4(bswap32((uint32_t)rs.total));
             hd.finish();
         }
-        emit_message(f, k, p + (Pos)HEAD, r, rs, inv_order, lists);
+        emit_message<PRES>(f, k, p + (Pos)HEAD, r, rs, inv_order, lists);
     }
 };
-
-// RuntimeEnc over a field set with a presence mask (PresentFields): the same bodies with PRES.
-struct RuntimePresentEnc {
-    struct Rec {};
-    template <class FS>
-    static __device__ __forceinline__ Rec load(const FS &, uint64_t) { return Rec{}; }
-    template <class FS>
-    static __device__ __forceinline__ void load_cols(const FS &, uint64_t, Rec &) {}
-    template <class FS>
-    static __device__ __forceinline__ void load_heaps(const FS &, Rec &) {}
-    template <class FS>
-    static __device__ __forceinline__ RecSize size(const FS &f, const Rec &, uint64_t r, bool check, bool &err) {
-        return record_size<true>(f, r, check, err);
-    }
-    template <int HEAD = 0, class Sink, class Pos, class FS, class Inv>
-    static __device__ __forceinline__ void emit(const FS &f, const Sink &k, Pos p, uint64_t r, const Rec &,
-                                                const RecSize &rs, const Inv *inv_order) {
-        if constexpr (HEAD != 0) {
-            static_assert(HEAD == 4, "the frame head is a u32");
-            Emit<Sink, Pos> hd(k, p);
-            hd.put4(bswap32((uint32_t)rs.total));
-            hd.finish();
-        }
-        emit_message<true>(f, k, p + (Pos)HEAD, r, rs, inv_order);
-    }
-};
+using RuntimeEnc = RuntimeEncT<false>;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t heap_rsrc(const EncFields &f, int i) {
     return uniform_rsrc(f.heaps[i], f.heap_lens[i]);

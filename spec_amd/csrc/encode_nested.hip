@@ -19,20 +19,13 @@ __global__ __launch_bounds__(NENC_BLOCK) void nested_enc_size_kernel(NestedEncod
     nested_enc_size_body<RuntimeEnc, RuntimeEnc>(a, smem);
 }
 
-__global__ __launch_bounds__(1024) void nested_enc_scan_kernel(NestedEncodeArgs a) {
-    scan_block_sums(a.block_sums, a.nblocks, a.total);
-}
-
 __global__ __launch_bounds__(NENC_BLOCK) void nested_enc_write_kernel(NestedEncodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     nested_enc_write_body<RuntimeEnc, RuntimeEnc>(a, smem);
 }
 
-// the framed encoder: 4 more bytes per record in every block sum, the head in front of every record
-__global__ __launch_bounds__(1024) void nested_enc_scan_frames_kernel(NestedEncodeArgs a) {
-    scan_block_sums<4>(a.block_sums, a.nblocks, a.total, a.n);
-}
-
+// the framed encoder: the head in front of every record (the shared scan, encode_flat.hip
+// launch_encode_scan, adds 4 more bytes per record to every block sum)
 __global__ __launch_bounds__(NENC_BLOCK) void nested_enc_write_frames_kernel(NestedEncodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     nested_enc_write_body<RuntimeEnc, RuntimeEnc, 4>(a, smem);
@@ -49,8 +42,7 @@ int launch_nested_encode(const spec_nested_schema *schema, const NestedEncodeArg
             hipLaunchKernelGGL(nested_enc_size_kernel, dim3((unsigned)a.nblocks), dim3(NENC_BLOCK),
                                nenc_size_lds_bytes(), stream, a);
     }
-    if (a.frame_head) hipLaunchKernelGGL(nested_enc_scan_frames_kernel, dim3(1), dim3(1024), 0, stream, a);
-    else hipLaunchKernelGGL(nested_enc_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+    launch_encode_scan(a.block_sums, a.nblocks, a.total, a.n, a.frame_head, stream);
     if (write && a.nblocks) {
         const int j = jit_launch_nested_encode(schema, a, true, stream);
         if (j < 0) return -1;

@@ -74,16 +74,10 @@ bool debug() {
     return e && e[0] && e[0] != '0';
 }
 
-// Table order a Writer produces (insertion sort, internal/writer/stack_msg.go:37-61).
-void writer_order(const spec_schema *s, uint8_t *order, uint16_t *sorted) {
-    for (uint32_t f = 0; f < s->nfields; f++) {
-        sorted[f] = s->fields[f].tag;
-        order[f] = (uint8_t)f;
-        for (int i = (int)f; i > 0 && sorted[i - 1] >= sorted[i]; i--) {
-            std::swap(sorted[i - 1], sorted[i]);
-            std::swap(order[i - 1], order[i]);
-        }
-    }
+// The Writer's table (spec_internal.hpp table_order) and its tags in that order.
+void writer_table(const spec_schema *s, uint8_t *order, uint16_t *sorted) {
+    spec::table_order(s, order);
+    for (uint32_t k = 0; k < s->nfields; k++) sorted[k] = s->fields[order[k]].tag;
 }
 
 // The flat decoder's fast path (decode_core.hpp fast_prepare / fast_wide) exists when the
@@ -95,7 +89,7 @@ bool has_flat_fast_path(const spec_schema *s) {
         if (s->fields[f].kind == SPEC_KIND_LIST) return false;
     uint8_t order[SPEC_KFIELDS];
     uint16_t sorted[SPEC_KFIELDS];
-    writer_order(s, order, sorted);
+    writer_table(s, order, sorted);
     for (uint32_t k = 0; k < s->nfields; k++) {
         if (sorted[k] == 0) return false;
         if (k && sorted[k] <= sorted[k - 1]) return false;
@@ -109,7 +103,7 @@ bool has_fast_path(const spec_schema *s) {
     if (s->nfields == 0 || s->nfields > (uint32_t)spec::FAST_MAX_FIELDS) return false;
     uint8_t order[SPEC_KFIELDS];
     uint16_t sorted[SPEC_KFIELDS];
-    writer_order(s, order, sorted);
+    writer_table(s, order, sorted);
     for (uint32_t k = 0; k < s->nfields; k++) {
         if (sorted[k] > 255 || sorted[k] == 0) return false;
         if (k && sorted[k] <= sorted[k - 1]) return false;
@@ -139,7 +133,7 @@ std::string key_of(const spec_schema *s, int device, Prog p) {
 void emit_spec(std::ostringstream &o, const char *name, const spec_schema *s) {
     uint8_t order[SPEC_KFIELDS];
     uint16_t sorted[SPEC_KFIELDS];
-    writer_order(s, order, sorted);
+    writer_table(s, order, sorted);
     uint8_t rank[SPEC_KFIELDS];
     for (uint32_t k = 0; k < s->nfields; k++) rank[order[k]] = (uint8_t)k;
     o << "struct " << name << " {\n  static constexpr int N = " << s->nfields << ";\n"
@@ -212,7 +206,7 @@ std::string generate_nested(const spec_nested_schema *s) {
 void emit_enc_spec(std::ostringstream &o, const char *name, const spec_schema *s) {
     uint8_t order[SPEC_KFIELDS];
     uint16_t sorted[SPEC_KFIELDS];
-    writer_order(s, order, sorted);
+    writer_table(s, order, sorted);
     bool big = false;
     o << "struct " << name << " {\n  static constexpr int N = " << s->nfields << ";\n"
       << "  static constexpr uint32_t kind[N] = {";

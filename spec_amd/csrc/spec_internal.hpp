@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/spec_amd.h"
 #include "decode_core.hpp"
 #include "encode_core.hpp"
@@ -12,6 +14,28 @@
 #include "decode_nested_core.hpp"
 
 namespace spec {
+
+// The hiprtc modules take spec::EncodeArgs by value as a raw parameter buffer, and the precompiled
+// kernels' argument segments are these blocks: their layouts do not move.
+static_assert(sizeof(EncodeArgs) == 1880 && sizeof(WideEncodeArgs) == 128, "flat encode argument blocks");
+static_assert(sizeof(PresentEncodeArgs) == 1896 && sizeof(WidePresentEncodeArgs) == 144,
+              "flat encode argument blocks with a presence mask");
+
+// Table order a Writer produces for this schema: messageStack.insert over the tags in write
+// order, insertion sort where an equal tag written later moves before the earlier one
+// (internal/writer/stack_msg.go:37-61).  order[j] = schema index of the j-th table entry.
+// The insertion moves a new entry left past every entry whose tag is >= its own, so the result
+// is the unique order by (tag ascending, write index descending): sorted in O(n log n) here
+// (a 1024-field schema in reverse tag order cost ~0.5 M swaps per call as an insertion sort).
+// The one definition behind EncFields::order, the wide field set's inv_order, FieldSet::rank and
+// the order[] constants of the schema-specialised kernels (jit.cpp).
+template <class T>
+void table_order(const spec_schema *s, T *order) {
+    uint32_t key[SPEC_MAX_FIELDS]; // tag << 16 | (0xffff - index): ascending = the Writer's order
+    for (uint32_t f = 0; f < s->nfields; f++) key[f] = (uint32_t)s->fields[f].tag << 16 | (0xffffu - f);
+    std::sort(key, key + s->nfields);
+    for (uint32_t j = 0; j < s->nfields; j++) order[j] = (T)(0xffffu - (key[j] & 0xffffu));
+}
 
 // The tree encoder's record-tile writer (jit.cpp gen_tile): waves per workgroup (= field blocks of
 // the records' table) and waves per SIMD the kernel is compiled for (amdgpu_waves_per_eu, its
@@ -75,7 +99,6 @@ int jit_prepare_encode_flat(const spec_schema *schema); // 1: jit_launch_encode 
 void jit_set_enabled(int on);
 long long jit_compile_only(const spec_schema *schema, double avg_record);
 long long jit_compile_only_encode(const spec_schema *schema);
-int launch_encode_size(const spec_schema *schema, const EncodeArgs &a, hipStream_t stream);
 // capi.hip: spec_encode_flat's passes (ENC_PASS_SIZE: sizes + scan into the workspace, heaps
 // checked; ENC_PASS_WRITE: the write pass over a workspace the size pass filled), every end
 // offset + ends_base (shard.hip: a shard's first byte in the whole batch).  frame_head = 4
@@ -85,14 +108,18 @@ int encode_flat_passes(const spec_schema *schema, const void *const *columns, co
                        const uint64_t *heap_lens, uint64_t n, uint8_t *out, uint64_t out_cap, uint64_t *ends,
                        uint64_t ends_base, void *workspace, size_t workspace_size, uint64_t *total, int passes,
                        hipStream_t stream, uint32_t frame_head = 0);
-int launch_encode_write(const spec_schema *schema, const EncodeArgs &a, hipStream_t stream);
-int launch_encode_wide_size(const WideEncodeArgs &a, hipStream_t stream);
-int launch_encode_wide_write(const WideEncodeArgs &a, hipStream_t stream);
-// encode_flat.hip: spec_encode_flat_present's passes (size + scan; write), narrow and wide
-int launch_encode_present_size(const PresentEncodeArgs &a, hipStream_t stream);
-int launch_encode_present_write(const PresentEncodeArgs &a, hipStream_t stream);
-int launch_encode_wide_present_size(const WidePresentEncodeArgs &a, hipStream_t stream);
-int launch_encode_wide_present_write(const WidePresentEncodeArgs &a, hipStream_t stream);
+// encode_flat.hip: the flat encoder's passes over any of the four argument blocks (EncodeArgs,
+// WideEncodeArgs, PresentEncodeArgs, WidePresentEncodeArgs): sizes + scan; write.  0, or -1 on a
+// HIP error.  The framed instantiations are chosen from a.frame_head, the schema-specialised
+// kernels (jit_launch_encode) tried for EncodeArgs alone.
+template <class A>
+int launch_encode_size(const spec_schema *schema, const A &a, hipStream_t stream);
+template <class A>
+int launch_encode_write(const spec_schema *schema, const A &a, hipStream_t stream);
+// pass 2 of the flat and nested encoders: one workgroup, block_sums[0, nblocks) -> exclusive
+// offsets and the total; frame_head bytes more for each of the n records
+void launch_encode_scan(uint64_t *block_sums, uint64_t nblocks, uint64_t *total, uint64_t n, uint32_t frame_head,
+                        hipStream_t stream);
 // jit.cpp: schema-specialised encode pass 1 (write=false) or 3; 1 launched, 0 use the
 // precompiled kernel, <0 HIP error.
 int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write, hipStream_t stream);
