@@ -1,4 +1,4 @@
-"""Embed device headers as C++ raw strings for hiprtc (jit.cpp): embed.py out.inc name=path..."""
+"""Embed device headers as C++ raw strings for hiprtc (jit_module.cpp): embed.py out.inc name=path..."""
 import sys
 
 out, pairs = sys.argv[1], sys.argv[2:]

@@ -37,7 +37,7 @@ void table_order(const spec_schema *s, T *order) {
     for (uint32_t j = 0; j < s->nfields; j++) order[j] = (T)(0xffffu - (key[j] & 0xffffu));
 }
 
-// The tree encoder's record-tile writer (jit.cpp gen_tile): waves per workgroup (= field blocks of
+// The tree encoder's record-tile writer (jit_tree.cpp gen_tile): waves per workgroup (= field blocks of
 // the records' table) and waves per SIMD the kernel is compiled for (amdgpu_waves_per_eu, its
 // register budget): 4 WPE / W workgroups per CU share the LDS, per workgroup the image of the
 // tile's output range and a dummy dword
@@ -96,7 +96,7 @@ long long jit_compile_only_nested(const spec_nested_schema *schema);
 int jit_launch_decode_flat(const spec_schema *schema, const DecodeArgs &a, double avg_record, hipStream_t stream);
 int jit_prepare_decode_flat(const spec_schema *schema, double avg_record);
 int jit_prepare_encode_flat(const spec_schema *schema); // 1: jit_launch_encode will launch, 0: it will not
-void jit_set_enabled(int on);
+void jit_set_enabled(int on); // jit_module.cpp
 long long jit_compile_only(const spec_schema *schema, double avg_record);
 long long jit_compile_only_encode(const spec_schema *schema);
 // capi.hip: spec_encode_flat's passes (ENC_PASS_SIZE: sizes + scan into the workspace, heaps
@@ -124,7 +124,7 @@ void launch_encode_scan(uint64_t *block_sums, uint64_t nblocks, uint64_t *total,
 // precompiled kernel, <0 HIP error.
 int jit_launch_encode(const spec_schema *schema, const EncodeArgs &a, bool write, hipStream_t stream);
 
-// jit.cpp: schema-specialised schema-tree group kernels (tree_decode.hip)
+// jit_tree.cpp: the kernels of a tree's generated module (tree.hip, tree_decode.hip)
 struct TreeDesc;
 const hipFunction_t *jit_tree_kernels(const TreeDesc &D);
 long long jit_compile_only_tree(const TreeDesc &D);

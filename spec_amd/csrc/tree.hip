@@ -648,7 +648,7 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
     B->frame_head = frame_head;
     const TreeDesc *Dd = (const TreeDesc *)(ws + w.desc);
     TreeBufs *Bd = (TreeBufs *)(ws + w.bufs);
-    // the generated writers and size passes (jit.cpp) for message tables, else the run-time row kernels
+    // the generated writers and size passes (jit_tree.cpp) for message tables, else the run-time row kernels
     const hipFunction_t *jit = jit_tree_kernels(L.desc);
     // level-fused launches (tree_core.hpp TableSet) when the generated module has them: the
     // tables of one height sized together (children have smaller heights), the tables of one
@@ -656,7 +656,7 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
     const bool sets = jit && jit[TREE_FN_SIZE_SET] && (jit[TREE_FN_WRITE_SET] || jit[TREE_FN_WRITE_TILE]);
     // the run-time writer keeps a message's field ends in LDS ([wave][field][lane], 256 B per field
     // per wave, 160 KiB per block at most): a table of more than 640 direct fields needs the
-    // generated writer (jit.cpp).  Checked before anything is issued, so a call that cannot run
+    // generated writer (jit_tree.cpp).  Checked before anything is issued, so a call that cannot run
     // leaves the stream, *total and out untouched.
     for (uint32_t x = 0; !sets && out && x < L.nt; x++)
         if (rows[x] && L.desc.t[x].shape == SHAPE_MESSAGE && (size_t)L.desc.t[x].nd * 64 * sizeof(uint32_t) > 163840) {
@@ -737,7 +737,7 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
             const TTable &T = L.desc.t[x];
             // a message's field ends live in LDS ([wave][field][lane], 256 B per field per wave):
             // fewer waves per block for a wide table (160 KiB per block at most); a table of more
-            // than 640 direct fields needs the generated writer (jit.cpp)
+            // than 640 direct fields needs the generated writer (jit_tree.cpp)
             const size_t per_wave = T.shape == SHAPE_MESSAGE ? (size_t)T.nd * 64 * sizeof(uint32_t) : 0;
             const unsigned wpb = per_wave ? (unsigned)std::min<size_t>(TB / 64, 163840 / per_wave) : TB / 64;
             if (wpb == 0) {

@@ -29,7 +29,7 @@
 namespace spec {
 namespace {
 
-// waves per 64 rows of the root group's staged kernel (jit.cpp gen_pair_rows; pkg1: 100 us
+// waves per 64 rows of the root group's staged kernel (jit_tree.cpp gen_pair_rows; pkg1: 100 us
 // against 158 us on one wave)
 constexpr uint32_t TREE_PAIR = 2;
 
@@ -253,7 +253,7 @@ struct spec_tree_decoder {
     int slot = 0;
     uint64_t rows[TREE_MAX_T] = {0}; // from the last index
     bool indexed = false;
-    const hipFunction_t *jit = nullptr; // schema-specialised group kernels (jit.cpp), per group root
+    const hipFunction_t *jit = nullptr; // schema-specialised group kernels (jit_tree.cpp), per group root
     bool jit_looked = false;
     ~spec_tree_decoder() {
         for (hipEvent_t &e : ev)

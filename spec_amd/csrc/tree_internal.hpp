@@ -23,7 +23,7 @@ struct Layout {
     TreeDesc desc;
 };
 
-// jit.cpp jit_tree_kernels(): the kernels of a tree's generated module by these indices, nullptr
+// jit_tree.cpp jit_tree_kernels(): the kernels of a tree's generated module by these indices, nullptr
 // where the module has none and the run-time kernel runs.
 enum TreeFn {
     TREE_FN_GROUP = 0,                   // + x: decode of group root x, rows staged in LDS

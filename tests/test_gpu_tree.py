@@ -122,7 +122,7 @@ def test_pkg1_root_pair_over_slab_and_stream_end(dev, case):
 
 @pytest.mark.parametrize("n,str_len", [(200, (0, 3000)), (3, (80_000, 100_000)), (130, (0, 600))])
 def test_pkg1_tiles_over_the_image(dev, n, str_len):
-    """The record-tile writer (jit.cpp gen_tile) on tiles whose output range exceeds its LDS image
+    """The record-tile writer (jit_tree.cpp gen_tile) on tiles whose output range exceeds its LDS image
     (36 KiB at 4 waves per workgroup): the bytes past the image's window go straight to HBM (tree_core.hpp LSink), whether
     64 records add up past it (25 KB records) or one record alone does (a 100 KB string), and a
     batch whose last tile is partial (130 records)."""

@@ -11,7 +11,8 @@ reader.  Every comparison is bit-exact against the oracle (oracle/tree.c).
   3. the encoder writes only out[0, total) and ends[0, n): canaries around both, `out` at odd
      byte phases within a 16-byte chunk;
   4. the write pass at capacity - 1, on encoder errors, on list rows no owner places, and the
-     run-time writer's refusal of a table too wide for its LDS.
+     run-time writer's refusal of a table too wide for its LDS;
+  5. a tree, a flat and a nested schema in turn through the one cache of generated modules.
 """
 from __future__ import annotations
 
@@ -165,7 +166,7 @@ def test_trees_encode_decode(dev, kernel, name):
     if name == "shapes_big":
         assert max(b.rows) > 255  # big lists (IsBigList by count)
     if name.startswith("many_tables"):
-        assert len(group_tables(b.tree, 0)) > 24  # no generated reader (jit.cpp tree_group_ok) ...
+        assert len(group_tables(b.tree, 0)) > 24  # no generated reader (jit_tree.cpp tree_group_ok) ...
         assert root_slab(b.tree, b.ends)[1] > WAVE_LDS_MAX  # ... and its range slots alone pass a wave's LDS
     check_encode_decode(b, dev)
 
@@ -173,7 +174,7 @@ def test_trees_encode_decode(dev, kernel, name):
 @pytest.mark.parametrize("n", [1, 300])
 def test_wide_encode_decode(dev, kernel, n):
     """wide_tree's root has more than 64 direct fields: no generated reader for its group
-    (jit.cpp tree_table_ok), no record-tile writer (tree_tile) — under "jit" the decode runs the
+    (jit_tree.cpp tree_table_ok), no record-tile writer (tree_tile) — under "jit" the decode runs the
     run-time group kernel and the encode the level-fused generated writer.  Its records are too
     long for a staging slab: the run-time group kernel parses them from HBM."""
     b = batch(f"wide_n{n}")
@@ -466,3 +467,75 @@ def test_runtime_writer_refuses_a_table_too_wide(dev):
         c.assert_untouched("641 fields")
     finally:
         spec_amd.set_jit(True)
+
+
+# ---- 5. several programs through the one module cache (jit_module.cpp) -------------------------
+
+def test_programs_share_one_module_cache(dev, capfd):
+    """A precompiled tree, FLAT16, NESTED and the same tree again, decode and encode each, in one
+    process with the generated kernels on: all five programs' modules go through the one cache
+    (jit_module.cpp find_module) and each keeps its own kernels.  65 records: a full 64-record
+    group and a one-record tail.  Every step against the oracle; the tree's second run equals its
+    first array for array.  The specialised kernels are the ones that ran: every module compiles
+    (or is read from the code-object cache), the flat launches answer for themselves
+    (require_specialised), and no module printed the cache's "compile/load failed" line."""
+    import ctypes as C
+
+    from oracle import oracle as O
+    from spec_amd.tree_catalog import precompiled_trees
+    from tests import gpu_helpers as G
+    from tests.test_gpu_nested import check_nested, nested_device_inputs
+
+    n = 65
+    spec_amd.set_jit(True)
+    L = spec_amd.lib()
+    tree = precompiled_trees()[1]
+    cols, heaps, rows = workload.tree_batch(tree, n, seed=165)
+    want_stream, want_ends = oracle_encode(tree, cols, heaps, n)
+    want_rows, want = oracle_decode(tree, want_stream, want_ends)
+
+    def run_tree():
+        assert L.spec_tree_jit_compile(C.byref(tree.c)) > 0
+        stream, ends = spec_amd.encode_tree(tree, to_dev(cols, dev), to_dev(heaps, dev), n, rows=rows)
+        torch.cuda.synchronize()
+        stream, ends = stream.cpu().numpy(), ends.cpu().numpy().view(np.uint64)
+        assert np.array_equal(ends, want_ends) and np.array_equal(stream, want_stream)
+        got_rows, got = decode_fresh(tree, want_stream, want_ends, dev)
+        assert got_rows == want_rows == rows
+        assert mismatches(tree, got, want) == []
+        return [stream, ends, np.array(got_rows)] + [g for g in got if g is not None]
+
+    first = run_tree()
+
+    flat = spec_amd.FLAT16
+    fcols, fheaps = workload.flat16(n, seed=65)
+    fstream, fends = G.oracle_encode(flat, fcols, fheaps, n)
+    G.require_specialised(flat, "FLAT16", decode=(fstream.size, n), encode=True)
+    G.check_decode(dev, flat, fstream, fends, "FLAT16 between trees")
+    G.check_encode(dev, flat, fcols, fheaps, n, "FLAT16 between trees")
+
+    w = workload.nested(n, seed=65, count=(1, 4))
+    counts = np.diff(w["item_begin"]).astype(np.int64)
+    counts[3], counts[10] = 0, 70  # an empty list, and one of more than a wave's 64 items
+    rng = np.random.default_rng(65)
+    m = int(counts.sum())
+    ib = np.zeros(n + 1, np.uint32)
+    np.cumsum(counts, out=ib[1:])
+    lens = rng.integers(0, 12, m).astype(np.uint32)
+    label = np.zeros((m, 2), np.uint32)
+    label[1:, 0] = np.cumsum(lens[:-1])
+    label[:, 1] = lens
+    w.update(item_begin=ib, key=rng.integers(-2**31, 2**31, m).astype(np.int32), value=rng.standard_normal(m),
+             label=label, label_heap=rng.integers(32, 127, int(lens.sum()), dtype=np.uint8))
+    assert L.spec_decode_nested_jit_compile(C.byref(spec_amd.NESTED.c)) > 0
+    assert L.spec_encode_nested_jit_compile(C.byref(spec_amd.NESTED.c)) > 0
+    nstream, nends = O.encode_nested_batch(w)
+    oc, oh, ibd, ic, ih = nested_device_inputs(w, dev)
+    out, ends = spec_amd.encode_nested(spec_amd.NESTED, oc, oh, ibd, ic, ih, n)
+    torch.cuda.synchronize()
+    assert np.array_equal(ends.cpu().numpy().view(np.uint64), nends) and np.array_equal(out.cpu().numpy(), nstream)
+    check_nested(dev, nstream, nends, "NESTED between trees", modes=("twopass-xcd", "onepass"))
+
+    again = run_tree()
+    assert len(first) == len(again) and all(np.array_equal(a, b) for a, b in zip(first, again))
+    assert "spec_amd jit:" not in capfd.readouterr().err
