@@ -13,6 +13,24 @@
  *  - Plain C types only; all buffers are caller-owned DEVICE pointers unless a name ends
  *    in _host.  `stream` is a hipStream_t passed as void* (NULL = default stream).
  *  - Return value: SPEC_OK (0) or a negative SPEC_E_* code; launches are asynchronous.
+ *  - The work of every call (kernels, uploads, memsets, scratch) is ordered on `stream` and on
+ *    nothing else (tests/test_gpu_streams.py), and spec_decode_flat (any field count, cold
+ *    schemas included), spec_encode_flat up to SPEC_KFIELDS fields, spec_parse_messages and
+ *    spec_tree_decoder_run (a decoder per thread) may be called from several host threads at
+ *    once, each on its own stream and buffers (tests/test_gpu_threads.py pins these and no
+ *    others).  The exceptions: a handle (spec_tree_decoder, spec_host_decoder, spec_shard) is used by one
+ *    thread and on one stream at a time; spec_set_jit and spec_set_nested_mode are process-wide
+ *    (a call reads them once: set them before the threads start); and these wait on the host:
+ *    spec_tree_decoder_index[_frames|_spans] (row counts), a spec_tree_decoder call that has to
+ *    grow the decoder's buffers, spec_tree_decoder_run[_frames] from the fifth call in flight,
+ *    spec_host_decoder_run[_frames], spec_shard_*, and the first call of a schema (hiprtc).
+ *    NOT covered, and known to be unsafe in one case: more than one call in flight, on one
+ *    stream or from several threads, of the entry points that upload per-call data from the
+ *    library's pinned pool - spec_encode_flat* of more than SPEC_KFIELDS fields,
+ *    spec_encode_tree[_frames], and spec_encode_nested[_frames] with a half of more than
+ *    SPEC_KFIELDS fields (it runs the tree encoder).  Four such flat encodes in flight on one
+ *    stream aborted the process, cause unknown; one at a time is tested.
+ *    Synchronise the stream between two of these calls and do not run them concurrently.
  *  - A batch is `stream_bytes[stream_len]` = records concatenated, and
  *    `ends[n]` = exclusive end offset of each record (record i = [ends[i-1], ends[i]),
  *    ends[-1] = 0): the layout an mpx receiver produces after framing
@@ -242,7 +260,9 @@ int spec_tree_layout(const spec_tree *tree, spec_tree_table *tables, uint32_t *n
  *     rows the caller's columns of each table hold (a BEGIN column holds its owner table's rows
  *     + 1 entries): rows are clamped to them, nothing is written past them (SPEC_E_CAPACITY if
  *     a record table's columns hold fewer than n rows).  With NULL, every list table's columns
- *     must hold spec_tree_decoder_capacity rows;
+ *     must hold spec_tree_decoder_capacity rows.  Each call stages its buffer table in one of 4
+ *     pinned slots: with 4 calls of one decoder still in flight the next one waits on the host
+ *     for the oldest (as does a call that has to grow a buffer: reserve first);
  *   spec_tree_decoder_capacity: the decoder's row capacity per list table (host; 0 for tables
  *     with a row per record);
  *   spec_tree_decoder_reserve: list-table capacities of at least rows[t] (host). */

@@ -17,6 +17,7 @@ code in libspec_amd.so.  Nothing here falls back to a CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 
@@ -30,6 +31,15 @@ from .schema import NP_DTYPE, VARLEN, Kind, Schema
 def _stream_handle(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+def _on(cuda_stream):
+    """The context in which a wrapper that allocates, zero-fills or reads back does so for a caller
+    who passed `cuda_stream`: that stream is made torch's current one, so the temporaries belong to
+    it in the caching allocator (a block freed at return is reused only behind the kernels that
+    still use it), a torch.zeros fill is ordered before those kernels and an .item() / .cpu() read
+    after them.  None (the caller's current stream): nothing changes."""
+    return torch.cuda.stream(cuda_stream) if cuda_stream is not None else contextlib.nullcontext()
 
 
 def _ptr(t: torch.Tensor | None):
@@ -273,14 +283,15 @@ def encode_flat_present(schema: Schema, cols, heaps: dict, present: torch.Tensor
     if n is None:
         n = cols[0].shape[0] if cols else 0
     dev = cols[0].device if cols else torch.device("cuda")
-    enc = Encoder(schema, n, dev)
-    total = int(enc.size_present(cols, heaps, present, frames, cuda_stream).item())
-    if total < 0:  # ~0: an encoder error (a written string/bytes span outside its heap or > MaxSize)
-        raise _lib.SpecError(-1, "spec_encode_flat_present: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    ends = torch.empty(n, dtype=torch.int64, device=dev)
-    (enc.encode_present_frames_into if frames else enc.encode_present_into)(cols, heaps, present, out, ends,
-                                                                            cuda_stream)
+    with _on(cuda_stream):
+        enc = Encoder(schema, n, dev)
+        total = int(enc.size_present(cols, heaps, present, frames, cuda_stream).item())
+        if total < 0:  # ~0: an encoder error (a written string/bytes span outside its heap or > MaxSize)
+            raise _lib.SpecError(-1, "spec_encode_flat_present: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ends = torch.empty(n, dtype=torch.int64, device=dev)
+        (enc.encode_present_frames_into if frames else enc.encode_present_into)(cols, heaps, present, out, ends,
+                                                                                cuda_stream)
     return out[:total], ends
 
 
@@ -289,15 +300,16 @@ def encode_flat(schema: Schema, cols, heaps: dict, n: int | None = None, cuda_st
     if n is None:
         n = cols[0].shape[0] if cols else 0
     dev = cols[0].device if cols else torch.device("cuda")
-    enc = Encoder(schema, n, dev)
-    total = int(enc.size(cols, cuda_stream).item())
-    if total < 0:  # ~0: an encoder error (string/bytes span outside its heap or > MaxSize)
-        raise _lib.SpecError(-1, "spec_encode_flat: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    ends = torch.empty(n, dtype=torch.int64, device=dev)
-    enc.encode_into(cols, heaps, out, ends, cuda_stream)
-    if int(enc.total.item()) != total:  # heap-range check failed in the full pass
-        raise _lib.SpecError(-1, "spec_encode_flat: encoder error (span outside its heap)")
+    with _on(cuda_stream):
+        enc = Encoder(schema, n, dev)
+        total = int(enc.size(cols, cuda_stream).item())
+        if total < 0:  # ~0: an encoder error (string/bytes span outside its heap or > MaxSize)
+            raise _lib.SpecError(-1, "spec_encode_flat: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ends = torch.empty(n, dtype=torch.int64, device=dev)
+        enc.encode_into(cols, heaps, out, ends, cuda_stream)
+        if int(enc.total.item()) != total:  # heap-range check failed in the full pass
+            raise _lib.SpecError(-1, "spec_encode_flat: encoder error (span outside its heap)")
     return out[:total], ends
 
 
@@ -307,16 +319,17 @@ def encode_flat_frames(schema: Schema, cols, heaps: dict, n: int | None = None, 
     if n is None:
         n = cols[0].shape[0] if cols else 0
     dev = cols[0].device if cols else torch.device("cuda")
-    enc = Encoder(schema, n, dev)
-    total = int(enc.size(cols, cuda_stream).item())
-    if total < 0:  # ~0: an encoder error (string/bytes span outside its heap or > MaxSize)
-        raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error")
-    total += 4 * n
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    ends = torch.empty(n, dtype=torch.int64, device=dev)
-    enc.encode_frames_into(cols, heaps, out, ends, cuda_stream)
-    if int(enc.total.item()) != total:  # heap-range check failed in the full pass
-        raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error (span outside its heap)")
+    with _on(cuda_stream):
+        enc = Encoder(schema, n, dev)
+        total = int(enc.size(cols, cuda_stream).item())
+        if total < 0:  # ~0: an encoder error (string/bytes span outside its heap or > MaxSize)
+            raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error")
+        total += 4 * n
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ends = torch.empty(n, dtype=torch.int64, device=dev)
+        enc.encode_frames_into(cols, heaps, out, ends, cuda_stream)
+        if int(enc.total.item()) != total:  # heap-range check failed in the full pass
+            raise _lib.SpecError(-1, "spec_encode_flat_frames: encoder error (span outside its heap)")
     return out[:total], ends
 
 

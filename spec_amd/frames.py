@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import Columns, _check_dev, _ptr, _stream_handle, alloc_columns
+from .batch import Columns, _check_dev, _on, _ptr, _stream_handle, alloc_columns
 from .schema import Schema
 
 
@@ -40,16 +40,17 @@ def frames_index_device(buf: torch.Tensor, cap: int | None = None, cuda_stream=N
     n = buf.numel()
     cap = cap if cap is not None else max(1, n // 4)
     dev = buf.device
-    ends = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-    out = torch.zeros(3, dtype=torch.int64, device=dev)  # count, consumed, status (int32 in slot 2)
-    L = _lib.lib()
-    ws_bytes = L.spec_frames_index_device_workspace_size(n)
-    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-    rc = L.spec_frames_index_device(_ptr(buf), n, _ptr(ends), cap, C.c_void_p(out.data_ptr()),
-                                    C.c_void_p(out.data_ptr() + 8), C.c_void_p(out.data_ptr() + 16), _ptr(ws),
-                                    ws_bytes, _stream_handle(cuda_stream))
-    _lib.check(rc, "spec_frames_index_device")
-    cnt, used, st = out.cpu().tolist()
+    with _on(cuda_stream):  # the zero fill before the kernels, the read after them, on their stream
+        ends = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        out = torch.zeros(3, dtype=torch.int64, device=dev)  # count, consumed, status (int32 in slot 2)
+        L = _lib.lib()
+        ws_bytes = L.spec_frames_index_device_workspace_size(n)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        rc = L.spec_frames_index_device(_ptr(buf), n, _ptr(ends), cap, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(out.data_ptr() + 8), C.c_void_p(out.data_ptr() + 16), _ptr(ws),
+                                        ws_bytes, _stream_handle(cuda_stream))
+        _lib.check(rc, "spec_frames_index_device")
+        cnt, used, st = out.cpu().tolist()
     st = st - (1 << 32) if st >= (1 << 31) else st  # int32 in the low half of the zeroed slot
     return ends[:cnt], used, st
 
@@ -137,7 +138,8 @@ def decode_frames_errors(schema: Schema, frames: torch.Tensor, ends: torch.Tenso
         status = torch.empty(n, dtype=torch.uint8, device=frames.device)
     words = max(1, (len(schema) + 63) // 64)
     if errmask is None:
-        errmask = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
+        with _on(cuda_stream):  # the zero fill runs on the decode's stream, before it
+            errmask = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
     ptrs = (C.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
     rc = _lib.lib().spec_decode_frames_errors(C.byref(schema.c), _ptr(frames), frames.numel(), _ptr(ends), r0, r1, 0,
                                               ptrs, _ptr(status), _ptr(errmask), _stream_handle(cuda_stream))
@@ -161,10 +163,11 @@ def decode_frames_present(schema: Schema, frames: torch.Tensor, ends: torch.Tens
     if status is None:
         status = torch.empty(n, dtype=torch.uint8, device=frames.device)
     words = max(1, (len(schema) + 63) // 64)
-    if present is None:
-        present = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
-    if errors and errmask is None:
-        errmask = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
+    with _on(cuda_stream):  # the zero fills run on the decode's stream, before it
+        if present is None:
+            present = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
+        if errors and errmask is None:
+            errmask = torch.zeros((words, max(r1, 1)), dtype=torch.int64, device=frames.device)
     ptrs = (C.c_void_p * max(1, len(cols)))(*[c.data_ptr() for c in cols])
     rc = _lib.lib().spec_decode_frames_present(C.byref(schema.c), _ptr(frames), frames.numel(), _ptr(ends), r0, r1, 0,
                                                ptrs, _ptr(status), _ptr(errmask if errors else None), _ptr(present),

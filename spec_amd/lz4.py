@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _check_dev, _ptr, _stream_handle
+from .batch import _check_dev, _on, _ptr, _stream_handle
 
 BLOCK_DTYPE = np.dtype([("src_off", "<u8"), ("src_len", "<u4"), ("stored", "<u4")])
 
@@ -63,7 +63,8 @@ class ContentChecksum:
         return self.out
 
     def digest(self, cuda_stream=None) -> int:
-        return int(self.digest_device(cuda_stream).item()) & 0xFFFFFFFF
+        with _on(cuda_stream):  # read on the stream that wrote it
+            return int(self.digest_device(cuda_stream).item()) & 0xFFFFFFFF
 
 
 def frame_blocks(buf: np.ndarray, state: Lz4State | None = None, cap: int | None = None):
@@ -94,22 +95,23 @@ def decompress(src: torch.Tensor, blocks: np.ndarray, block_max: int, cuda_strea
     dev = src.device
     nb = len(blocks)
     L = _lib.lib()
-    d_blocks = torch.from_numpy(np.ascontiguousarray(blocks).view(np.uint8).copy()).to(dev)
-    slot = max(int(block_max), 4)
-    slots = torch.empty(max(nb, 1) * slot, dtype=torch.uint8, device=dev)
-    sizes = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
-    status = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-    s = _stream_handle(cuda_stream)
-    rc = L.spec_lz4_decompress(_ptr(src), src.numel(), _ptr(d_blocks), nb, _ptr(slots), slot, _ptr(sizes),
-                               _ptr(status), s)
-    _lib.check(rc, "spec_lz4_decompress")
-    out = torch.empty(max(nb, 1) * slot, dtype=torch.uint8, device=dev)
-    wsb = L.spec_lz4_pack_workspace_size(nb)
-    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
-    rc = L.spec_lz4_pack(_ptr(slots), slot, _ptr(sizes), nb, _ptr(out), out.numel(), _ptr(total), _ptr(ws), wsb, s)
-    _lib.check(rc, "spec_lz4_pack")
-    t = int(total.item())
+    with _on(cuda_stream):  # the block table's upload, the temporaries and the read of total: on that stream
+        d_blocks = torch.from_numpy(np.ascontiguousarray(blocks).view(np.uint8).copy()).to(dev)
+        slot = max(int(block_max), 4)
+        slots = torch.empty(max(nb, 1) * slot, dtype=torch.uint8, device=dev)
+        sizes = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+        status = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        s = _stream_handle(cuda_stream)
+        rc = L.spec_lz4_decompress(_ptr(src), src.numel(), _ptr(d_blocks), nb, _ptr(slots), slot, _ptr(sizes),
+                                   _ptr(status), s)
+        _lib.check(rc, "spec_lz4_decompress")
+        out = torch.empty(max(nb, 1) * slot, dtype=torch.uint8, device=dev)
+        wsb = L.spec_lz4_pack_workspace_size(nb)
+        ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        rc = L.spec_lz4_pack(_ptr(slots), slot, _ptr(sizes), nb, _ptr(out), out.numel(), _ptr(total), _ptr(ws), wsb, s)
+        _lib.check(rc, "spec_lz4_pack")
+        t = int(total.item())
     if t < 0:
         raise _lib.SpecError(-6, "spec_lz4_decompress: corrupt block")
     return out[:t], sizes[:nb].view(torch.int32), status[:nb]
@@ -154,14 +156,14 @@ def compress_frame(data: torch.Tensor, block_max: int = 256 << 10, open: bool = 
     everything the frame contains, this call's data included, when `close` is set."""
     flags = (OPEN if open else 0) | (CLOSE if close else 0) | (CONTENT_CHECKSUM if content is not None else 0)
     dev = data.device
-    out = torch.empty(frame_bound(data.numel(), block_max, flags), dtype=torch.uint8, device=dev)
-    total = torch.zeros(1, dtype=torch.int64, device=dev)
-    digest = content.digest_device(cuda_stream) if (content is not None and close) else None
-    ws = compress_frame_into(data, out, total, block_max, flags, digest, cuda_stream=cuda_stream)
-    if cuda_stream is not None:
-        torch.cuda.synchronize(dev)  # total and the workspace belong to that stream
-    del ws
-    return out[: int(total.item())]
+    with _on(cuda_stream):  # total's zero fill and read and the workspace belong to that stream
+        out = torch.empty(frame_bound(data.numel(), block_max, flags), dtype=torch.uint8, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        digest = content.digest_device(cuda_stream) if (content is not None and close) else None
+        ws = compress_frame_into(data, out, total, block_max, flags, digest, cuda_stream=cuda_stream)
+        t = int(total.item())
+        del ws
+    return out[:t]
 
 
 class Lz4Writer:

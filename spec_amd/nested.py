@@ -18,7 +18,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .batch import _check_dev, _ptr, _stream_handle, alloc_columns
+from .batch import _check_dev, _on, _ptr, _stream_handle, alloc_columns
 from .schema import Kind, NestedSchema
 
 
@@ -102,8 +102,9 @@ class NestedDecoder:
         return self.total
 
     def result(self) -> NestedColumns:
-        return NestedColumns(self.schema, self.outer, self.status, self.item_begin, self.items, self.item_status,
-                             int(self.total.item()))
+        with _on(self.cuda_stream):  # the total is written on that stream: read it there
+            total = int(self.total.item())
+        return NestedColumns(self.schema, self.outer, self.status, self.item_begin, self.items, self.item_status, total)
 
 
 def decode_nested(schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor, cuda_stream=None,
@@ -111,18 +112,19 @@ def decode_nested(schema: NestedSchema, stream: torch.Tensor, ends: torch.Tensor
     """Two-pass: index, size the item columns from the device total, decode.  onepass: decode
     into item_cap items (default 4 per record) in one pass; if the batch holds more, grow the
     item columns to the reported total and decode again."""
-    d = NestedDecoder(schema, stream, ends, cuda_stream, head)
-    if onepass:
-        d.reserve(max(1, item_cap if item_cap is not None else 4 * d.n))
-        total = int(d.decode_onepass().item())
-        if total > d.item_cap:
-            d.reserve(total)
-            d.decode_onepass()
+    with _on(cuda_stream):
+        d = NestedDecoder(schema, stream, ends, cuda_stream, head)
+        if onepass:
+            d.reserve(max(1, item_cap if item_cap is not None else 4 * d.n))
+            total = int(d.decode_onepass().item())
+            if total > d.item_cap:
+                d.reserve(total)
+                d.decode_onepass()
+            return d.result()
+        total = int(d.index().item())
+        d.reserve(total)
+        d.decode()
         return d.result()
-    total = int(d.index().item())
-    d.reserve(total)
-    d.decode()
-    return d.result()
 
 
 def decode_nested_frames(schema: NestedSchema, frames: torch.Tensor, ends: torch.Tensor, cuda_stream=None,
@@ -189,15 +191,16 @@ def encode_nested(schema: NestedSchema, outer_cols, outer_heaps, item_begin, ite
                   cuda_stream=None):
     """-> (stream uint8[total], ends int64[n]) on the device."""
     dev = item_begin.device
-    enc = NestedEncoder(schema, n, dev)
-    nitems = item_cols[0].shape[0] if item_cols else 0
-    total = int(enc.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems,
-                           cuda_stream=cuda_stream).item())
-    if total < 0:
-        raise _lib.SpecError(-1, "spec_encode_nested: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    ends = torch.empty(n, dtype=torch.int64, device=dev)
-    enc.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
+    with _on(cuda_stream):
+        enc = NestedEncoder(schema, n, dev)
+        nitems = item_cols[0].shape[0] if item_cols else 0
+        total = int(enc.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems,
+                               cuda_stream=cuda_stream).item())
+        if total < 0:
+            raise _lib.SpecError(-1, "spec_encode_nested: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ends = torch.empty(n, dtype=torch.int64, device=dev)
+        enc.encode(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
     return out[:total], ends
 
 
@@ -206,13 +209,14 @@ def encode_nested_frames(schema: NestedSchema, outer_cols, outer_heaps, item_beg
     """Encode a batch straight to mpx frames -> (frames uint8[total + 4n], frame_ends int64[n]) on the
     device: the bytes and ends of frames.write_frames(*encode_nested(...)), in the encoder's launches."""
     dev = item_begin.device
-    enc = NestedEncoder(schema, n, dev)
-    nitems = item_cols[0].shape[0] if item_cols else 0
-    total = int(enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems,
-                                  cuda_stream=cuda_stream).item())
-    if total < 0:
-        raise _lib.SpecError(-1, "spec_encode_nested_frames: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    ends = torch.empty(n, dtype=torch.int64, device=dev)
-    enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
+    with _on(cuda_stream):
+        enc = NestedEncoder(schema, n, dev)
+        nitems = item_cols[0].shape[0] if item_cols else 0
+        total = int(enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems,
+                                      cuda_stream=cuda_stream).item())
+        if total < 0:
+            raise _lib.SpecError(-1, "spec_encode_nested_frames: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        ends = torch.empty(n, dtype=torch.int64, device=dev)
+        enc.encode_frames(outer_cols, outer_heaps, item_begin, item_cols, item_heaps, nitems, out, ends, cuda_stream)
     return out[:total], ends

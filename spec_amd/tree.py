@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .batch import _on
 from .schema import WIDTH, Kind
 
 SCALARS = tuple(Kind(k) for k in range(1, 16))
@@ -485,30 +486,34 @@ class TreeEncoder:
 
 def encode_tree(tree: Tree, cols: dict, heaps: dict, n: int, rows=None, cuda_stream=None):
     """-> (stream uint8 [total], ends int64 [n]) on the device."""
-    rows = rows if rows is not None else tree_rows(tree, n, cols)
     some = next(v for v in cols.values() if v is not None)
-    enc = TreeEncoder(tree, rows, some.device)
-    total = int(enc.encode(cols, heaps, None, None, cuda_stream).item())
-    if total < 0:
-        raise _lib.SpecError(-1, "spec_encode_tree: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
-    ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
-    enc.encode(cols, heaps, out, ends, cuda_stream)
+    with _on(cuda_stream):
+        # (tree_rows reads the BEGIN columns back: on the stream the caller filled them on)
+        rows = rows if rows is not None else tree_rows(tree, n, cols)
+        enc = TreeEncoder(tree, rows, some.device)
+        total = int(enc.encode(cols, heaps, None, None, cuda_stream).item())
+        if total < 0:
+            raise _lib.SpecError(-1, "spec_encode_tree: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
+        ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
+        enc.encode(cols, heaps, out, ends, cuda_stream)
     return out[:total], ends[:n]
 
 
 def encode_tree_frames(tree: Tree, cols: dict, heaps: dict, n: int, rows=None, cuda_stream=None):
     """Encode a batch straight to mpx frames -> (frames uint8 [total + 4n], frame_ends int64 [n]) on
     the device: the bytes and ends of frames.write_frames(*encode_tree(...)), in the encoder's launches."""
-    rows = rows if rows is not None else tree_rows(tree, n, cols)
     some = next(v for v in cols.values() if v is not None)
-    enc = TreeEncoder(tree, rows, some.device)
-    total = int(enc.encode_frames(cols, heaps, None, None, cuda_stream).item())
-    if total < 0:
-        raise _lib.SpecError(-1, "spec_encode_tree_frames: encoder error")
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
-    ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
-    enc.encode_frames(cols, heaps, out, ends, cuda_stream)
+    with _on(cuda_stream):
+        # (tree_rows reads the BEGIN columns back: on the stream the caller filled them on)
+        rows = rows if rows is not None else tree_rows(tree, n, cols)
+        enc = TreeEncoder(tree, rows, some.device)
+        total = int(enc.encode_frames(cols, heaps, None, None, cuda_stream).item())
+        if total < 0:
+            raise _lib.SpecError(-1, "spec_encode_tree_frames: encoder error")
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=some.device)
+        ends = torch.empty(max(n, 1), dtype=torch.int64, device=some.device)
+        enc.encode_frames(cols, heaps, out, ends, cuda_stream)
     return out[:total], ends[:n]
 
 
