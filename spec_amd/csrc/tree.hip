@@ -6,7 +6,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <vector>
 
@@ -165,33 +164,7 @@ __global__ __launch_bounds__(TB) void tree_write_kernel(const TreeDesc *Dp, cons
 
 // ---- exclusive scans ---------------------------------------------------------------------
 
-constexpr int SCAN_T = 1024, SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER;
-
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *sh, uint64_t &block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) sh[wave] = incl;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-        uint64_t acc = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
-            const uint64_t t = sh[w];
-            sh[w] = acc;
-            acc += t;
-        }
-        sh[16] = acc;
-    }
-    lds_barrier();
-    const uint64_t r = sh[wave] + incl - v;
-    block_total = sh[16];
-    lds_barrier();
-    return r;
-}
+constexpr int SCAN_PER = 4, SCAN_TILE = SCAN_T * SCAN_PER; // (SCAN_T, block_excl_scan: tree_internal.hpp)
 
 // pass 1: tile sums of a u32 array; every element counts `add` more (the framed encoder's head
 // per record, 0 otherwise)
@@ -229,7 +202,6 @@ __global__ __launch_bounds__(SCAN_T) void scan_top_kernel(uint64_t *tile_sums, u
 // own starts, past their heads (the framed tree encoder: message starts).  fold (up to FOLD_TILES tiles, no pass 2):
 // the tile's offset is the sum of the earlier tiles' totals, summed by the block itself (one load
 // per thread), and block 0 sums every tile into *total (all-ones when *err).
-constexpr uint64_t FOLD_TILES = 1024;
 __global__ __launch_bounds__(SCAN_T) void scan_apply_kernel(const uint32_t *in, uint64_t n, const uint64_t *tile_sums,
                                                             uint64_t *total, uint32_t *out32, uint64_t *out64,
                                                             uint64_t *ends64, uint32_t fold, const uint32_t *err,
@@ -278,13 +250,13 @@ __global__ __launch_bounds__(256) void tree_pos_fill_kernel(PosFill f) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) p[i] = ~0ull;
 }
 
-size_t scan_ws_bytes(uint64_t n) { return ((n + SCAN_TILE - 1) / SCAN_TILE + 1) * sizeof(uint64_t); }
+size_t scan_ws_bytes(uint64_t n) { return (scan_tiles(n, SCAN_TILE) + 1) * sizeof(uint64_t); }
 
 // exclusive scan of in[0, n) (in place allowed for out32); *total (device) = the sum, or all-ones
 // when *err (optional) is set.  add: `add` bytes in front of every element (scan_apply_kernel)
 int launch_scan(const uint32_t *in, uint64_t n, uint32_t *out32, uint64_t *out64, uint64_t *ends64, uint64_t *ws,
                 uint64_t *total, const uint32_t *err, hipStream_t st, uint32_t add = 0) {
-    const uint64_t tiles = std::max<uint64_t>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
+    const uint64_t tiles = std::max<uint64_t>(1, scan_tiles(n, SCAN_TILE));
     const uint32_t fold = tiles <= FOLD_TILES ? 1u : 0u;
     hipLaunchKernelGGL(scan_tiles_kernel, dim3((unsigned)tiles), dim3(SCAN_T), 0, st, in, n, ws, add);
     if (!fold) hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(SCAN_T), 0, st, ws, tiles, total, err);
@@ -499,18 +471,16 @@ extern "C" {
 
 int spec_tree_layout(const spec_tree *tree, spec_tree_table *tables, uint32_t *ntables, spec_tree_column *columns,
                      uint32_t *ncolumns) {
-    Layout *L = new (std::nothrow) Layout();
+    const std::unique_ptr<Layout> L = make_layout(tree);
     if (!L) return SPEC_E_INVALID_ARGUMENT;
-    const bool ok = build_layout(tree, *L);
-    if (ok) {
-        if (tables) memcpy(tables, L->tables, sizeof(spec_tree_table) * L->nt);
-        if (columns) memcpy(columns, L->cols, sizeof(spec_tree_column) * L->nc);
-        if (ntables) *ntables = L->nt;
-        if (ncolumns) *ncolumns = L->nc;
-    }
-    delete L;
-    return ok ? SPEC_OK : SPEC_E_INVALID_ARGUMENT;
+    if (tables) memcpy(tables, L->tables, sizeof(spec_tree_table) * L->nt);
+    if (columns) memcpy(columns, L->cols, sizeof(spec_tree_column) * L->nc);
+    if (ntables) *ntables = L->nt;
+    if (ncolumns) *ncolumns = L->nc;
+    return SPEC_OK;
 }
+
+} // extern "C"
 
 // ---- encode ----
 
@@ -518,8 +488,6 @@ namespace {
 struct EncWs {
     size_t desc, bufs, size[TREE_MAX_T], pos[TREE_MAX_T], offsets, scan, err, total, tblk, tmask;
 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // [desc | bufs | err] first and contiguous: ONE upload (from a pinned slot) sets all three, the
 // error word to zero
@@ -553,9 +521,7 @@ size_t enc_plan(const Layout &L, const uint64_t *rows, EncWs &w) {
     o += align256(std::max<uint64_t>(rows[0], 1) * sizeof(uint64_t));
     return o;
 }
-} // namespace
 
-namespace {
 // copies the workspace head [desc | bufs | err = 0] (ENC_HEAD bytes) to the device on st through
 // the library's pinned upload pool (spec::pinned_upload: no host wait on the device); false on a
 // HIP error
@@ -566,21 +532,144 @@ bool upload_head(const TreeDesc &desc, const TreeBufs &bufs, void *dhead, hipStr
     memcpy(h.data() + ENC_HEAD_BUFS, &bufs, sizeof(TreeBufs));
     return spec::pinned_upload(dhead, h.data(), ENC_HEAD, st) == hipSuccess;
 }
-} // namespace
 
-size_t spec_encode_tree_workspace_size(const spec_tree *tree, const uint64_t *rows) {
-    Layout *L = new (std::nothrow) Layout();
-    if (!L || !rows || !build_layout(tree, *L)) {
-        delete L;
-        return 0;
+// ---- the phases of one encode call (encode_tree_passes), in the order they are issued ----
+
+struct EncCall {
+    const Layout &L;
+    const TreeBufs &B;  // the call's buffer block (host copy)
+    const TreeDesc *Dd; // the descriptor and the block in the workspace head (device)
+    TreeBufs *Bd;
+    hipStream_t st;
+    const hipFunction_t *sets; // the generated module's level-fused kernels, or null: the run-time row kernels
+};
+
+// Fills B's columns, heaps, rows and per-table workspace pointers.  INVALID_ARGUMENT: an input
+// column or a span column's heap missing where its table has rows, a sub-message table (REL_ONE)
+// whose rows are not its owner's.
+int bind_columns(const Layout &L, const EncWs &w, uint8_t *ws, const void *const *columns, const uint8_t *const *heaps,
+                 const uint64_t *heap_lens, const uint64_t *rows, TreeBufs &B) {
+    for (uint32_t c = 0; c < L.nc; c++) {
+        B.cols[c] = (void *)columns[c];
+        B.heaps[c] = heaps ? heaps[c] : nullptr;
+        B.heap_lens[c] = heap_lens ? heap_lens[c] : 0;
+        const spec_tree_column &col = L.cols[c];
+        const bool spans = col.role == SPEC_COL_VALUE && (col.kind == SPEC_KIND_STRING || col.kind == SPEC_KIND_BYTES ||
+                                                         col.kind == SPEC_KIND_ANY);
+        // a BEGIN column has owner rows + 1 entries: needed whenever the owner table has rows
+        // (an owner whose lists are all empty still reads begin[row], begin[row + 1])
+        const uint64_t col_rows = col.role == SPEC_COL_BEGIN ? rows[L.tables[col.table].parent] : rows[col.table];
+        const bool input = col.role == SPEC_COL_VALUE || col.role == SPEC_COL_PRESENT || col.role == SPEC_COL_BEGIN;
+        if (input && !columns[c] && col_rows) return SPEC_E_INVALID_ARGUMENT;
+        if (spans && rows[col.table] && !B.heaps[c]) return SPEC_E_INVALID_ARGUMENT;
     }
-    EncWs w;
-    const size_t s = enc_plan(*L, rows, w);
-    delete L;
-    return s;
+    for (uint32_t x = 0; x < L.nt; x++) {
+        B.rows[x] = rows[x];
+        B.size[x] = (uint32_t *)(ws + w.size[x]);
+        B.pos[x] = x ? (uint64_t *)(ws + w.pos[x]) : nullptr;
+        if (L.tables[x].rel == SPEC_REL_ONE && rows[x] != rows[L.tables[x].parent]) return SPEC_E_INVALID_ARGUMENT;
+    }
+    return SPEC_OK;
 }
 
-} // extern "C"
+// Waves per block of the run-time writer (tree_write_kernel) for table T, 0: T does not fit.  A
+// message's field ends live in LDS ([wave][field][lane], 256 B per field per wave, 160 KiB per
+// block at most): fewer waves for a wide table, and a table of more than 640 direct fields needs
+// the generated writer (jit_tree.cpp).
+size_t field_ends_bytes(const TTable &T) { // per wave
+    return T.shape == SHAPE_MESSAGE ? (size_t)T.nd * 64 * sizeof(uint32_t) : 0;
+}
+unsigned write_waves(const TTable &T) {
+    const size_t per_wave = field_ends_bytes(T);
+    return per_wave ? (unsigned)std::min<size_t>(TB / 64, 163840 / per_wave) : TB / 64;
+}
+
+// The tables by level: height (a leaf table 0: children have smaller heights, so they are sized
+// first) and depth (the records 0: owners have smaller depths, so they are written first).
+struct Levels {
+    int height[TREE_MAX_T] = {0}, depth[TREE_MAX_T] = {0};
+    explicit Levels(const Layout &L) {
+        for (uint32_t x = 1; x < L.nt; x++) depth[x] = depth[L.desc.t[x].parent] + 1;
+        for (int x = (int)L.nt - 1; x > 0; x--) {
+            const int par = L.desc.t[x].parent;
+            height[par] = std::max(height[par], height[x] + 1);
+        }
+    }
+};
+
+// Level-fused launches of fn, a level after the other: the level's tables that have rows,
+// blockIdx.y picking the table.
+bool launch_sets(const EncCall &e, hipFunction_t fn, const int *level) {
+    const int top = *std::max_element(level, level + e.L.nt);
+    for (int lv = 0; lv <= top; lv++) {
+        TableSet ts;
+        ts.n = 0;
+        uint64_t most = 0;
+        for (uint32_t x = 0; x < e.L.nt; x++)
+            if (level[x] == lv && e.B.rows[x]) {
+                ts.t[ts.n++] = x;
+                most = std::max(most, e.B.rows[x]);
+            }
+        void *args[] = {(void *)&e.Dd, (void *)&e.Bd, &ts};
+        if (ts.n && !launch_tree_fn(fn, row_grid(most), ts.n, TB, 0, e.st, args)) return false;
+    }
+    return true;
+}
+
+// Every row's encoded size: level-fused by height, or the run-time kernel table by table
+// bottom-up (children before their owners: table order is pre-order).
+bool size_pass(const EncCall &e, const Levels &v) {
+    if (e.sets) return launch_sets(e, e.sets[TREE_FN_SIZE_SET], v.height);
+    for (int x = (int)e.L.nt - 1; x >= 0; x--)
+        if (const uint64_t rows = e.B.rows[x])
+            hipLaunchKernelGGL(tree_size_kernel, dim3(row_grid(rows)), dim3(TB), 0, e.st, e.Dd, e.Bd, (uint32_t)x, rows);
+    return true;
+}
+
+// Record offsets and *total (all-ones on an encoder error); no records: *total = 0.
+bool record_scan(const EncCall &e, uint64_t *scan_ws) {
+    const TreeBufs &B = e.B;
+    if (!B.n) return hipMemsetAsync(B.total, 0, sizeof(uint64_t), e.st) == hipSuccess;
+    return launch_scan(B.size[0], B.n, nullptr, B.offsets, nullptr, scan_ws, B.total, B.err, e.st, B.frame_head) == 0;
+}
+
+// The bytes: the record-tile writer, or a level-fused writer per depth, or the run-time writer
+// table by table top-down.
+bool write_pass(const EncCall &e, const Levels &v) {
+    const Layout &L = e.L;
+    if (e.sets && e.sets[TREE_FN_WRITE_TILE]) {
+        if (!e.B.n) return true;
+        uint32_t cap = TREE_TILE_IMG;
+        void *args[] = {(void *)&e.Dd, (void *)&e.Bd, &cap};
+        return launch_tree_fn(e.sets[TREE_FN_WRITE_TILE], (unsigned)((e.B.n + 63) / 64), 1, 64 * TREE_TILE_W,
+                              TREE_TILE_IMG + 16, e.st, args);
+    }
+    if (e.sets) return launch_sets(e, e.sets[TREE_FN_WRITE_SET], v.depth);
+    // child rows start unplaced: only rows their owner writes get a position (the generated
+    // writers mark the rows under an absent or unplaced owner themselves)
+    PosFill pf;
+    uint64_t most = 0;
+    for (uint32_t x = 1; x < L.nt; x++) {
+        pf.p[x - 1] = e.B.pos[x];
+        pf.n[x - 1] = e.B.rows[x];
+        most = std::max(most, e.B.rows[x]);
+    }
+    if (most) {
+        const unsigned gx = (unsigned)std::min<uint64_t>((most + 255) / 256, 1024);
+        hipLaunchKernelGGL(tree_pos_fill_kernel, dim3(gx, L.nt - 1), dim3(256), 0, e.st, pf);
+    }
+    for (uint32_t x = 0; x < L.nt; x++)
+        if (const uint64_t rows = e.B.rows[x]) {
+            const TTable &T = L.desc.t[x];
+            const unsigned wpb = write_waves(T); // (not 0: encode_tree_passes checked before issuing anything)
+            const uint64_t blocks = std::min<uint64_t>((rows + 64 * wpb - 1) / (64 * wpb),
+                                                       (uint64_t)row_grid(rows) * (TB / 64) / wpb);
+            hipLaunchKernelGGL(tree_write_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(64 * wpb),
+                               wpb * field_ends_bytes(T), e.st, e.Dd, e.Bd, x, rows);
+        }
+    return true;
+}
+} // namespace
 
 // spec_encode_tree (frame_head 0) and spec_encode_tree_frames (4: every record behind its mpx
 // frame head, written by the record's own root writer; the same launches)
@@ -589,177 +678,53 @@ int spec::encode_tree_passes(const spec_tree *tree, const void *const *columns, 
                              uint64_t *ends, void *workspace, size_t workspace_size, uint64_t *total, void *stream,
                              uint32_t frame_head) {
     if (!columns || !rows || !total || !workspace) return SPEC_E_INVALID_ARGUMENT;
-    Layout *Lp = new (std::nothrow) Layout();
+    const std::unique_ptr<Layout> Lp = make_layout(tree);
     if (!Lp) return SPEC_E_INVALID_ARGUMENT;
-    if (!build_layout(tree, *Lp)) {
-        delete Lp;
-        return SPEC_E_INVALID_ARGUMENT;
-    }
-    Layout &L = *Lp;
+    const Layout &L = *Lp;
     EncWs w;
-    if (enc_plan(L, rows, w) > workspace_size) {
-        delete Lp;
-        return SPEC_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    if (enc_plan(L, rows, w) > workspace_size) return SPEC_E_WORKSPACE;
     uint8_t *ws = (uint8_t *)workspace;
-    TreeBufs *B = new (std::nothrow) TreeBufs();
-    if (!B) {
-        delete Lp;
-        return SPEC_E_INVALID_ARGUMENT;
-    }
-    memset(B, 0, sizeof(*B));
-    int rc = SPEC_OK;
-    for (uint32_t c = 0; c < L.nc; c++) {
-        B->cols[c] = (void *)columns[c];
-        B->heaps[c] = heaps ? heaps[c] : nullptr;
-        B->heap_lens[c] = heap_lens ? heap_lens[c] : 0;
-        const spec_tree_column &col = L.cols[c];
-        const bool spans = col.role == SPEC_COL_VALUE && (col.kind == SPEC_KIND_STRING || col.kind == SPEC_KIND_BYTES ||
-                                                         col.kind == SPEC_KIND_ANY);
-        // a BEGIN column has owner rows + 1 entries: needed whenever the owner table has rows
-        // (an owner whose lists are all empty still reads begin[row], begin[row + 1])
-        const uint64_t col_rows = col.role == SPEC_COL_BEGIN ? rows[L.tables[col.table].parent] : rows[col.table];
-        const bool input = col.role == SPEC_COL_VALUE || col.role == SPEC_COL_PRESENT || col.role == SPEC_COL_BEGIN;
-        if (input && !columns[c] && col_rows) rc = SPEC_E_INVALID_ARGUMENT;
-        if (spans && rows[col.table] && !B->heaps[c]) rc = SPEC_E_INVALID_ARGUMENT;
-    }
-    for (uint32_t x = 0; x < L.nt; x++) {
-        B->rows[x] = rows[x];
-        B->size[x] = (uint32_t *)(ws + w.size[x]);
-        B->pos[x] = x ? (uint64_t *)(ws + w.pos[x]) : nullptr;
-        if (L.tables[x].rel == SPEC_REL_ONE && rows[x] != rows[L.tables[x].parent]) rc = SPEC_E_INVALID_ARGUMENT;
-    }
-    if (rc) {
-        delete B;
-        delete Lp;
-        return rc;
-    }
-    const uint64_t n = rows[0];
-    B->n = n;
-    B->out = out;
-    B->out_cap = out ? out_cap : 0;
-    B->ends_out = ends;
-    B->offsets = (uint64_t *)(ws + w.offsets);
-    B->tblk = (uint32_t *)(ws + w.tblk);
-    B->tmask = (uint64_t *)(ws + w.tmask);
-    B->total = total;
-    B->err = (uint32_t *)(ws + w.err);
-    B->frame_head = frame_head;
-    const TreeDesc *Dd = (const TreeDesc *)(ws + w.desc);
-    TreeBufs *Bd = (TreeBufs *)(ws + w.bufs);
-    // the generated writers and size passes (jit_tree.cpp) for message tables, else the run-time row kernels
+    const std::unique_ptr<TreeBufs> Bp(new (std::nothrow) TreeBufs());
+    if (!Bp) return SPEC_E_INVALID_ARGUMENT;
+    TreeBufs &B = *Bp;
+    memset(&B, 0, sizeof(B));
+    if (const int rc = bind_columns(L, w, ws, columns, heaps, heap_lens, rows, B)) return rc;
+    B.n = rows[0];
+    B.out = out;
+    B.out_cap = out ? out_cap : 0;
+    B.ends_out = ends;
+    B.offsets = (uint64_t *)(ws + w.offsets);
+    B.tblk = (uint32_t *)(ws + w.tblk);
+    B.tmask = (uint64_t *)(ws + w.tmask);
+    B.total = total;
+    B.err = (uint32_t *)(ws + w.err);
+    B.frame_head = frame_head;
+    // the generated size passes and writers (jit_tree.cpp), level-fused (tree_core.hpp TableSet): the
+    // tables of one height sized together, of one depth written together
     const hipFunction_t *jit = jit_tree_kernels(L.desc);
-    // level-fused launches (tree_core.hpp TableSet) when the generated module has them: the
-    // tables of one height sized together (children have smaller heights), the tables of one
-    // depth written together (owners have smaller depths)
     const bool sets = jit && jit[TREE_FN_SIZE_SET] && (jit[TREE_FN_WRITE_SET] || jit[TREE_FN_WRITE_TILE]);
-    // the run-time writer keeps a message's field ends in LDS ([wave][field][lane], 256 B per field
-    // per wave, 160 KiB per block at most): a table of more than 640 direct fields needs the
-    // generated writer (jit_tree.cpp).  Checked before anything is issued, so a call that cannot run
-    // leaves the stream, *total and out untouched.
-    for (uint32_t x = 0; !sets && out && x < L.nt; x++)
-        if (rows[x] && L.desc.t[x].shape == SHAPE_MESSAGE && (size_t)L.desc.t[x].nd * 64 * sizeof(uint32_t) > 163840) {
-            delete B;
-            delete Lp;
-            return SPEC_E_TOO_LARGE;
-        }
-    bool ok = upload_head(L.desc, *B, ws, st);
-    int height[TREE_MAX_T] = {0}, depth[TREE_MAX_T] = {0}, maxh = 0, maxd = 0;
-    for (uint32_t x = 1; x < L.nt; x++) depth[x] = depth[L.desc.t[x].parent] + 1;
-    for (int x = (int)L.nt - 1; x > 0; x--) {
-        const int par = L.desc.t[x].parent;
-        height[par] = std::max(height[par], height[x] + 1);
-    }
-    for (uint32_t x = 0; x < L.nt; x++) {
-        maxh = std::max(maxh, height[x]);
-        maxd = std::max(maxd, depth[x]);
-    }
-    auto launch_set = [&](hipFunction_t fn, const int *level, int lv) -> bool {
-        TableSet ts;
-        ts.n = 0;
-        uint64_t most = 0;
-        for (uint32_t x = 0; x < L.nt; x++)
-            if (level[x] == lv && rows[x]) {
-                ts.t[ts.n++] = x;
-                most = std::max(most, rows[x]);
-            }
-        if (!ts.n) return true;
-        void *args[] = {(void *)&Dd, (void *)&Bd, &ts};
-        const hipError_t le = hipModuleLaunchKernel(fn, row_grid(most), ts.n, 1, TB, 1, 1, 0, st, args, nullptr);
-        if (le != hipSuccess) note_hip_error(le);
-        return le == hipSuccess;
-    };
-    for (int h = 0; sets && ok && h <= maxh; h++) ok = launch_set(jit[TREE_FN_SIZE_SET], height, h);
-    // (no generated module: the run-time row kernels) sizes bottom-up (children before their
-    // owners: table order is pre-order)
-    for (int x = (int)L.nt - 1; !sets && ok && x >= 0; x--)
-        if (rows[x])
-            hipLaunchKernelGGL(tree_size_kernel, dim3(row_grid(rows[x])), dim3(TB), 0, st, Dd, Bd, (uint32_t)x, rows[x]);
-    // record offsets, total (all-ones on an encoder error)
-    if (ok) {
-        if (n) {
-            ok = launch_scan(B->size[0], n, nullptr, B->offsets, nullptr, (uint64_t *)(ws + w.scan), total, B->err,
-                             st, frame_head) == 0;
-        } else {
-            ok = hipMemsetAsync(total, 0, sizeof(uint64_t), st) == hipSuccess;
-        }
-    }
-    // child rows start unplaced: only rows their owner writes get a position (the generated
-    // writers mark the rows under an absent or unplaced owner themselves)
-    if (!sets && ok && out && L.nt > 1) {
-        PosFill pf;
-        uint64_t most = 0;
-        for (uint32_t x = 1; x < L.nt; x++) {
-            pf.p[x - 1] = B->pos[x];
-            pf.n[x - 1] = rows[x];
-            most = std::max(most, rows[x]);
-        }
-        if (most) {
-            const unsigned gx = (unsigned)std::min<uint64_t>((most + 255) / 256, 1024);
-            hipLaunchKernelGGL(tree_pos_fill_kernel, dim3(gx, L.nt - 1), dim3(256), 0, st, pf);
-        }
-    }
-    const bool tile = sets && jit[TREE_FN_WRITE_TILE];
-    if (tile && ok && out && n) {
-        uint32_t cap = TREE_TILE_IMG;
-        void *args[] = {(void *)&Dd, (void *)&Bd, &cap};
-        const hipError_t le = hipModuleLaunchKernel(jit[TREE_FN_WRITE_TILE], (unsigned)((n + 63) / 64), 1, 1,
-                                                    64 * TREE_TILE_W, 1, 1, TREE_TILE_IMG + 16, st, args,
-                                                    nullptr);
-        if (le != hipSuccess) note_hip_error(le);
-        ok = le == hipSuccess;
-    }
-    for (int d = 0; sets && !tile && ok && out && d <= maxd; d++) ok = launch_set(jit[TREE_FN_WRITE_SET], depth, d);
-    bool too_wide = false;
-    for (uint32_t x = 0; !sets && ok && out && !too_wide && x < L.nt; x++)
-        if (rows[x]) {
-            const TTable &T = L.desc.t[x];
-            // a message's field ends live in LDS ([wave][field][lane], 256 B per field per wave):
-            // fewer waves per block for a wide table (160 KiB per block at most); a table of more
-            // than 640 direct fields needs the generated writer (jit_tree.cpp)
-            const size_t per_wave = T.shape == SHAPE_MESSAGE ? (size_t)T.nd * 64 * sizeof(uint32_t) : 0;
-            const unsigned wpb = per_wave ? (unsigned)std::min<size_t>(TB / 64, 163840 / per_wave) : TB / 64;
-            if (wpb == 0) {
-                too_wide = true;
-                break;
-            }
-            const uint64_t blocks = std::min<uint64_t>((rows[x] + 64 * wpb - 1) / (64 * wpb), (uint64_t)row_grid(rows[x]) * (TB / 64) / wpb);
-            hipLaunchKernelGGL(tree_write_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(64 * wpb), wpb * per_wave, st,
-                               Dd, Bd, x, rows[x]);
-        }
-    const hipError_t e = hipGetLastError();
-    delete B;
-    delete Lp;
-    if (too_wide) return SPEC_E_TOO_LARGE;
-    if (!ok || e != hipSuccess) {
-        note_hip_error(e);
-        return SPEC_E_HIP;
-    }
-    return SPEC_OK;
+    const EncCall e{L, B, (const TreeDesc *)(ws + w.desc), (TreeBufs *)(ws + w.bufs), (hipStream_t)stream,
+                    sets ? jit : nullptr};
+    // a table the run-time writer cannot take: refused before anything is issued, so the call leaves
+    // the stream, *total and out untouched
+    for (uint32_t x = 0; !e.sets && out && x < L.nt; x++)
+        if (rows[x] && write_waves(L.desc.t[x]) == 0) return SPEC_E_TOO_LARGE;
+    const Levels v(L);
+    const bool ok = upload_head(L.desc, B, ws, e.st) && size_pass(e, v) && record_scan(e, (uint64_t *)(ws + w.scan)) &&
+                    (!out || write_pass(e, v));
+    const hipError_t err = hipGetLastError(); // the run-time kernels' launches
+    note_hip_error(err);
+    return ok && err == hipSuccess ? SPEC_OK : SPEC_E_HIP;
 }
 
 extern "C" {
+
+size_t spec_encode_tree_workspace_size(const spec_tree *tree, const uint64_t *rows) {
+    const std::unique_ptr<Layout> L = make_layout(tree);
+    if (!L || !rows) return 0;
+    EncWs w;
+    return enc_plan(*L, rows, w);
+}
 
 int spec_encode_tree(const spec_tree *tree, const void *const *columns, const uint8_t *const *heaps,
                      const uint64_t *heap_lens, const uint64_t *rows, uint8_t *out, uint64_t out_cap, uint64_t *ends,

@@ -52,35 +52,7 @@ __global__ __launch_bounds__(TB) void tree_group_kernel(const TreeDesc *Dp, cons
 // ---- the group's list counts -> CSR begin, row counts, element ranges ----------------------
 
 // one owner row per thread: the apply pass's per-row element loads are the latency to hide
-constexpr int SCAN_T = 1024, SCAN_PER = 1, SCAN_TILE = SCAN_T * SCAN_PER;
-
-// Exclusive block scan through LDS (lds_barrier, spec_device.hpp: a caller's loads issued before it
-// overlap it).
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *sh, uint64_t &block_total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) sh[wave] = incl;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-        uint64_t acc = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
-            const uint64_t t = sh[w];
-            sh[w] = acc;
-            acc += t;
-        }
-        sh[16] = acc;
-    }
-    lds_barrier();
-    const uint64_t r = sh[wave] + incl - v;
-    block_total = sh[16];
-    lds_barrier();
-    return r;
-}
+constexpr int SCAN_PER = 1, SCAN_TILE = SCAN_T * SCAN_PER; // (SCAN_T, block_excl_scan: tree_internal.hpp)
 
 // The list tables scanned together (every list owned in one group: same owner rows).
 struct ListSet {
@@ -104,13 +76,12 @@ __global__ __launch_bounds__(SCAN_T) void list_tiles_kernel(const TreeDesc *Dp, 
     for (int k = 0; k < SCAN_PER; k++)
         if (base + k < rows) v += cnt[base + k];
     uint64_t tot;
-    block_scan(v, sh, tot);
+    block_excl_scan(v, sh, tot);
     if (threadIdx.x == 0) m.ws[blockIdx.y][blockIdx.x] = tot;
 }
 
 // Many tiles (owner rows > FOLD_TILES tiles): per list j (blockIdx.x), exclusive offsets of the
 // tile totals in place, and the list's row count (rows_out_kernel compares it with the capacity).
-constexpr uint64_t FOLD_TILES = 1024;
 __global__ __launch_bounds__(SCAN_T) void list_top_kernel(const TreeDesc *Dp, const TreeBufs *Bp, ListSet m) {
     __shared__ uint64_t sh[17];
     const TreeDesc &D = *Dp;
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(SCAN_T) void list_top_kernel(const TreeDesc *Dp, co
         const uint64_t i = b + threadIdx.x;
         const uint64_t v = i < ntiles ? ws[i] : 0;
         uint64_t tot;
-        const uint64_t e = block_scan(v, sh, tot);
+        const uint64_t e = block_excl_scan(v, sh, tot);
         if (i < ntiles) ws[i] = carry + e;
         carry += tot;
     }
@@ -162,8 +133,8 @@ __global__ __launch_bounds__(SCAN_T) void list_apply_kernel(const TreeDesc *Dp, 
     for (uint64_t i = threadIdx.x; i < lim; i += SCAN_T) part += tiles[i];
     const uint64_t t0 = v0 ? load_le64(gs, (long long)h.x) : 0, t1 = v0 ? load_le64(gs, (long long)h.x + 8) : 0;
     uint64_t sum = 0, tot;
-    if (!m.top) (void)block_scan(part, sh, sum); // sum: earlier tiles (block 0: every tile)
-    uint64_t p = (m.top ? tiles[blockIdx.x] : (blockIdx.x ? sum : 0)) + block_scan(v0, sh, tot);
+    if (!m.top) (void)block_excl_scan(part, sh, sum); // sum: earlier tiles (block 0: every tile)
+    uint64_t p = (m.top ? tiles[blockIdx.x] : (blockIdx.x ? sum : 0)) + block_excl_scan(v0, sh, tot);
     const uint32_t v[1] = {v0};
     for (int k = 0; k < SCAN_PER; k++) {
         if (r >= rows) break;
@@ -305,6 +276,14 @@ unsigned group_waves(uint32_t wave_bytes) {
 
 int grow(DevBuf &b, size_t bytes) { return b.reserve(std::max<size_t>(bytes, 256)); }
 
+// Rows that group root x can hold in a batch of n records: the records, or its list's capacity.
+uint64_t group_cap(const spec_tree_decoder *d, uint32_t x, uint64_t n) { return x == 0 ? n : d->caps[x]; }
+
+// Scan workspace of one list whose owner group holds `cap` rows: a word per tile of owner rows and
+// one more, 256-byte aligned.  The one formula behind prepare()'s reservation and plan_groups'
+// carve.
+size_t list_scan_ws(uint64_t cap) { return align256((scan_tiles(cap, SCAN_TILE) + 1) * sizeof(uint64_t)); }
+
 // Buffers for the batch (n records) and the current list capacities; fills d->B.
 int prepare(spec_tree_decoder *d, uint64_t n) {
     Layout &L = d->L;
@@ -312,11 +291,10 @@ int prepare(spec_tree_decoder *d, uint64_t n) {
     const TreeDesc &D = L.desc;
     for (uint32_t x = 1; x < L.nt; x++) {
         const TTable &T = D.t[x];
-        const uint64_t cap = T.groot == 0 ? n : d->caps[T.groot];
+        const uint64_t cap = group_cap(d, T.groot, n);
         B.caps[x] = cap;
         if (T.rel == REL_MANY) {
-            const uint32_t o = T.parent;
-            const uint64_t ocap = D.t[o].groot == 0 ? n : d->caps[D.t[o].groot];
+            const uint64_t ocap = group_cap(d, D.t[T.parent].groot, n);
             if (grow(d->rng[x], std::max<uint64_t>(cap, 1) * sizeof(uint2)) ||
                 grow(d->cnt[x], (ocap + 1) * sizeof(uint32_t)) || grow(d->lh[x], std::max<uint64_t>(ocap, 1) * sizeof(uint4)))
                 return SPEC_E_HIP;
@@ -326,16 +304,11 @@ int prepare(spec_tree_decoder *d, uint64_t n) {
         }
     }
     B.caps[0] = n;
-    // scan workspace: per list table, the tile sums of its owner rows
+    // scan workspace: per list table, the tile sums of its owner rows (and 256 bytes of slack each)
     size_t ws = 0;
-    for (uint32_t x = 1; x < L.nt; x++) {
-        if (D.t[x].rel != REL_MANY) continue;
-        const uint32_t o = D.t[D.t[x].parent].groot;
-        const uint64_t ocap = o == 0 ? n : d->caps[o];
-        ws += ((ocap + SCAN_TILE - 1) / SCAN_TILE + 1) * sizeof(uint64_t) + 256;
-    }
-    if (grow(d->ws_scan, ws)) return SPEC_E_HIP;
-    return SPEC_OK;
+    for (uint32_t x = 1; x < L.nt; x++)
+        if (D.t[x].rel == REL_MANY) ws += list_scan_ws(group_cap(d, D.t[D.t[x].parent].groot, n)) + 256;
+    return grow(d->ws_scan, ws) ? SPEC_E_HIP : SPEC_OK;
 }
 
 // Upload d->B if it differs from what the device holds (stream-ordered, from pinned staging).
@@ -353,6 +326,117 @@ int upload(spec_tree_decoder *d, hipStream_t st) {
     return SPEC_OK;
 }
 
+// ---- the phases of one decode pass (run), in the order they are issued ----
+
+struct DecCall {
+    const spec_tree_decoder *d;
+    uint64_t n, stream_len;
+    const TreeDesc *Dd; // the descriptor and the call's block on the device
+    const TreeBufs *Bd;
+    hipStream_t st;
+    const hipFunction_t *gen; // the generated kernels; null when a column is null: they store every column
+};
+
+// Groups by level: the records' group is level 0, a list's group one level below its owner's
+// group.  The groups of one level are independent (their rows come from the previous level's
+// scans); every list owned in a group gets one batched scan after the group's kernel.
+constexpr uint32_t NO_LEVEL = ~0u; // a table decoded inside its group
+struct GroupPlan {
+    uint32_t lv[TREE_MAX_T], maxlv = 0;
+    ListSet lists[TREE_MAX_T]; // per group root: the lists it owns, each with its scan workspace
+};
+
+void plan_groups(const spec_tree_decoder *d, uint64_t n, GroupPlan &p) {
+    const Layout &L = d->L;
+    const TreeDesc &D = L.desc;
+    uint8_t *wsp = (uint8_t *)d->ws_scan.p;
+    for (uint32_t x = 0; x < L.nt; x++) {
+        p.lv[x] = NO_LEVEL;
+        if (D.t[x].groot != x) continue;
+        p.lv[x] = x ? p.lv[D.t[D.t[x].parent].groot] + 1 : 0; // the owner's group precedes it
+        p.maxlv = std::max(p.maxlv, p.lv[x]);
+        const uint64_t cap = group_cap(d, x, n);
+        ListSet &m = p.lists[x];
+        m.n = 0;
+        m.owner = x;
+        m.top = scan_tiles(cap, SCAN_TILE) > FOLD_TILES ? 1u : 0u;
+        for (uint32_t y = x + 1; y < L.nt; y++) {
+            if (D.t[y].rel != REL_MANY || D.t[D.t[y].parent].groot != x) continue;
+            m.y[m.n] = y;
+            m.ws[m.n++] = (uint64_t *)wsp;
+            wsp += list_scan_ws(cap);
+        }
+    }
+}
+
+// The level's groups that generated kernels parse from HBM: picked, and when there are two or more
+// run as ONE level-fused launch (pkg1's five list groups: 89.5 -> 70.5 us) and marked in in_set; a
+// single one is left to its own kernel.
+bool launch_fused_set(const DecCall &c, const GroupPlan &p, uint32_t level, bool *in_set) {
+    const spec_tree_decoder *d = c.d;
+    TableSet fused;
+    fused.n = 0;
+    uint32_t wave_bytes = 16;
+    unsigned grid = 1;
+    for (uint32_t x = 1; c.gen && c.gen[TREE_FN_GROUP_SET] && x < d->L.nt; x++) {
+        if (p.lv[x] != level || d->caps[x] == 0 || !c.gen[TREE_FN_GROUP + x]) continue;
+        const GroupShape gs = group_shape(d->L, x, c.stream_len, d->caps[x]);
+        if (gs.slab) continue;
+        fused.t[fused.n++] = x;
+        wave_bytes = std::max(wave_bytes, gs.wave_bytes);
+        grid = std::max(grid, row_grid(d->caps[x]));
+    }
+    if (fused.n < 2) return true;
+    for (uint32_t j = 0; j < fused.n; j++) in_set[fused.t[j]] = true;
+    void *args[] = {(void *)&c.Dd, (void *)&c.Bd, &fused, &wave_bytes};
+    const unsigned fw = group_waves(wave_bytes);
+    return launch_tree_fn(c.gen[TREE_FN_GROUP_SET], grid, fused.n, 64 * fw, fw * wave_bytes, c.st, args);
+}
+
+// Group root x's kernel: the generated pair kernel (the root group on P waves per 64 rows), the
+// generated kernel over staged rows or rows from HBM, or the run-time tree_group_kernel.
+bool launch_group(const DecCall &c, uint32_t x) {
+    const spec_tree_decoder *d = c.d;
+    const uint64_t cap = group_cap(d, x, c.n);
+    if (cap == 0) return true;
+    const GroupShape gs = group_shape(d->L, x, c.stream_len, cap);
+    const unsigned wpb = group_waves(gs.wave_bytes);
+    const uint64_t per_block = (uint64_t)wpb * gs.rpw;
+    const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((cap + per_block - 1) / per_block, 1u << 20));
+    const unsigned lds = wpb * gs.wave_bytes;
+    uint32_t xx = x, slab = gs.slab, wb = gs.wave_bytes, rpw = gs.rpw;
+    if (c.gen && gs.slab && c.gen[TREE_FN_GROUP_PAIR + x]) {
+        // one slab, the waves decoding it (tree_rows_pair), one set of range slots, a 1 KiB exchange
+        // per extra wave (pkg1: 35 KiB slab + 2 KiB slots + 1-3 KiB = four blocks per CU)
+        const uint32_t gn = d->L.desc.t[x].gn, P = TREE_PAIR;
+        uint32_t slots = 512u * (gn > 1 ? gn - 1 : 0);
+        rpw = 64;
+        void *args[] = {(void *)&c.Dd, (void *)&c.Bd, &xx, &slab, &slots, &rpw};
+        const unsigned grid = (unsigned)std::min<uint64_t>((cap + 63) / 64, 1u << 20);
+        return launch_tree_fn(c.gen[TREE_FN_GROUP_PAIR + x], grid, 1, 64 * P, slab + slots + (P - 1) * 1024, c.st, args);
+    }
+    if (c.gen && c.gen[TREE_FN_GROUP + x]) {
+        void *args[] = {(void *)&c.Dd, (void *)&c.Bd, &xx, &slab, &wb, &rpw};
+        // rows from HBM: the kernel without staging code (fewer registers, more waves)
+        const hipFunction_t hbm = c.gen[TREE_FN_GROUP_HBM + x];
+        const hipFunction_t fn = gs.slab == 0 && hbm ? hbm : c.gen[TREE_FN_GROUP + x];
+        return launch_tree_fn(fn, gs.slab == 0 ? row_grid(cap) : (unsigned)blocks, 1, 64 * wpb, lds, c.st, args);
+    }
+    hipLaunchKernelGGL(tree_group_kernel, dim3((unsigned)blocks), dim3(64 * wpb), lds, c.st, c.Dd, c.Bd, x, gs.slab,
+                       gs.wave_bytes, gs.rpw);
+    return true;
+}
+
+// Every list owned in group x: one batched scan (tiles, the top pass beyond FOLD_TILES tiles, apply)
+void launch_list_scans(const DecCall &c, const ListSet &m) {
+    const uint64_t cap = group_cap(c.d, m.owner, c.n);
+    if (!m.n || cap == 0) return;
+    const unsigned tiles = (unsigned)std::max<uint64_t>(1, scan_tiles(cap, SCAN_TILE));
+    hipLaunchKernelGGL(list_tiles_kernel, dim3(tiles, m.n), dim3(SCAN_T), 0, c.st, c.Dd, c.Bd, m);
+    if (m.top) hipLaunchKernelGGL(list_top_kernel, dim3(m.n), dim3(SCAN_T), 0, c.st, c.Dd, c.Bd, m);
+    hipLaunchKernelGGL(list_apply_kernel, dim3(tiles, m.n), dim3(SCAN_T), 0, c.st, c.Dd, c.Bd, m);
+}
+
 // The whole decode of a batch, asynchronous on st: every group's kernel, then its lists' scans.
 // col_rows (optional, host, per table): rows the caller's columns hold; every group's rows are
 // clamped to them (its tables' columns, and the BEGIN columns of the lists it owns: owner rows +
@@ -367,8 +451,7 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
     Layout &L = d->L;
     TreeBufs &B = d->B;
     const TreeDesc &D = L.desc;
-    int rc = prepare(d, n);
-    if (rc) return rc;
+    if (const int rc = prepare(d, n)) return rc;
     if (col_rows) {
         for (uint32_t x = 0; x < L.nt; x++) {
             const uint32_t g = D.t[x].groot;
@@ -378,7 +461,7 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
                 B.caps[g] = std::min(B.caps[g], col_rows[x]);
             }
         }
-        for (uint32_t x = 1; x < L.nt; x++) B.caps[x] = B.caps[D.t[x].groot == 0 ? 0 : D.t[x].groot];
+        for (uint32_t x = 1; x < L.nt; x++) B.caps[x] = B.caps[D.t[x].groot];
         B.caps[0] = n;
     }
     B.stream = stream_bytes;
@@ -388,12 +471,12 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
     B.head = spans ? 0 : head;
     B.n = n;
     B.rowsd = (uint64_t *)d->misc.p;
-    bool all_cols = columns != nullptr; // the schema-specialised kernels store every column unconditionally
+    bool all_cols = columns != nullptr;
     for (uint32_t c = 0; c < L.nc; c++) {
         B.cols[c] = columns ? columns[c] : nullptr;
         all_cols = all_cols && B.cols[c];
     }
-    if ((rc = upload(d, st))) return rc;
+    if (const int rc = upload(d, st)) return rc;
     // a group with no capacity yet is skipped, and with it the scans of the lists it owns: their
     // row counts must read 0, not a previous batch's (and n == 0 skips every scan)
     bool skipped = n == 0;
@@ -403,121 +486,21 @@ int run(spec_tree_decoder *d, const uint8_t *stream_bytes, uint64_t stream_len, 
         d->jit = jit_tree_kernels(D);
         d->jit_looked = true;
     }
-    const TreeDesc *Dd = (const TreeDesc *)d->desc.p;
-    const TreeBufs *Bd = (const TreeBufs *)d->bufs.p;
-    uint8_t *wsp = (uint8_t *)d->ws_scan.p;
-    // Groups by level: the records' group is level 0, a list's group one level below its owner's
-    // group.  The groups of one level are independent (their rows come from the previous level's
-    // scans); every list owned in a group gets one batched scan after the group's kernel.
-    uint32_t lv[TREE_MAX_T] = {};
-    uint32_t maxlv = 0;
-    ListSet ms[TREE_MAX_T];
-    for (uint32_t x = 0; x < L.nt; x++) {
-        if (D.t[x].groot != x) continue; // decoded inside its group
-        if (x) lv[x] = lv[D.t[D.t[x].parent].groot] + 1; // the owner's group precedes it
-        maxlv = std::max(maxlv, lv[x]);
-        const uint64_t cap = x == 0 ? n : d->caps[x];
-        ListSet &m = ms[x];
-        m.n = 0;
-        m.owner = x;
-        m.top = (cap + SCAN_TILE - 1) / SCAN_TILE > FOLD_TILES ? 1u : 0u;
-        for (uint32_t y = x + 1; y < L.nt; y++) {
-            if (D.t[y].rel != REL_MANY || D.t[D.t[y].parent].groot != x) continue;
-            m.y[m.n] = y;
-            m.ws[m.n] = (uint64_t *)wsp;
-            wsp += (((cap + SCAN_TILE - 1) / SCAN_TILE + 1) * sizeof(uint64_t) + 255) & ~(size_t)255;
-            m.n++;
-        }
-    }
-    const hipFunction_t set_fn = d->jit && all_cols ? d->jit[TREE_FN_GROUP_SET] : nullptr;
-    for (uint32_t level = 0; n && level <= maxlv; level++) {
-        // the level's groups parsed from HBM by generated kernels: one level-fused launch when
-        // there are two or more (pkg1's five list groups: 89.5 -> 70.5 us)
+    const DecCall c{d, n, stream_len, (const TreeDesc *)d->desc.p, (const TreeBufs *)d->bufs.p, st,
+                    all_cols ? d->jit : nullptr};
+    GroupPlan plan;
+    plan_groups(d, n, plan);
+    for (uint32_t level = 0; n && level <= plan.maxlv; level++) {
         bool in_set[TREE_MAX_T] = {};
-        TableSet fused;
-        fused.n = 0;
-        uint32_t fused_wb = 16;
-        unsigned fused_grid = 1;
-        for (uint32_t x = 1; set_fn && x < L.nt; x++) {
-            if (D.t[x].groot != x || lv[x] != level || d->caps[x] == 0 || !d->jit[TREE_FN_GROUP + x]) continue;
-            const GroupShape gs = group_shape(L, x, stream_len, d->caps[x]);
-            if (gs.slab) continue;
-            fused.t[fused.n++] = x;
-            fused_wb = std::max(fused_wb, gs.wave_bytes);
-            fused_grid = std::max(fused_grid, row_grid(d->caps[x]));
-        }
-        if (fused.n >= 2) { // (one group: its own kernel below)
-            for (uint32_t j = 0; j < fused.n; j++) in_set[fused.t[j]] = true;
-            void *args[] = {(void *)&Dd, (void *)&Bd, &fused, &fused_wb};
-            const unsigned fw = group_waves(fused_wb);
-            const hipError_t le = hipModuleLaunchKernel(set_fn, fused_grid, fused.n, 1, 64 * fw, 1, 1,
-                                                        (unsigned)(fw * fused_wb), st, args, nullptr);
-            if (le != hipSuccess) {
-                note_hip_error(le);
-                return SPEC_E_HIP;
-            }
-        }
-        for (uint32_t x = 0; x < L.nt; x++) {
-            if (D.t[x].groot != x || lv[x] != level || in_set[x]) continue;
-            const uint64_t cap = x == 0 ? n : d->caps[x];
-            if (cap == 0) continue;
-            const GroupShape gs = group_shape(L, x, stream_len, cap);
-            const unsigned wpb = group_waves(gs.wave_bytes);
-            const uint64_t per_block = (uint64_t)wpb * gs.rpw;
-            const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((cap + per_block - 1) / per_block, 1u << 20));
-            const size_t lds = (size_t)wpb * gs.wave_bytes;
-            const hipFunction_t pair_fn =
-                d->jit && all_cols && gs.slab ? d->jit[TREE_FN_GROUP_PAIR + x] : nullptr;
-            if (pair_fn) {
-                // the root group on P waves per 64 rows: one slab, the waves decoding it
-                // (tree_rows_pair), one set of range slots, a 1 KiB exchange per extra wave (pkg1:
-                // 35 KiB slab + 2 KiB slots + 1-3 KiB = four blocks per CU)
-                const uint32_t gn = D.t[x].gn, P = TREE_PAIR;
-                uint32_t xx = x, slab = gs.slab, slots = 512u * (gn > 1 ? gn - 1 : 0), rpw = 64;
-                void *args[] = {(void *)&Dd, (void *)&Bd, &xx, &slab, &slots, &rpw};
-                const unsigned grid = (unsigned)std::min<uint64_t>((cap + 63) / 64, 1u << 20);
-                const hipError_t le = hipModuleLaunchKernel(pair_fn, grid, 1, 1, 64 * P, 1, 1, slab + slots + (P - 1) * 1024,
-                                                            st, args, nullptr);
-                if (le != hipSuccess) {
-                    note_hip_error(le);
-                    return SPEC_E_HIP;
-                }
-            } else if (d->jit && d->jit[TREE_FN_GROUP + x] && all_cols) {
-                uint32_t xx = x, slab = gs.slab, wb = gs.wave_bytes, rpw = gs.rpw;
-                void *args[] = {(void *)&Dd, (void *)&Bd, &xx, &slab, &wb, &rpw};
-                // rows from HBM: the kernel without staging code (fewer registers, more waves)
-                const hipFunction_t hbm = d->jit[TREE_FN_GROUP_HBM + x];
-                const hipFunction_t fn = gs.slab == 0 && hbm ? hbm : d->jit[TREE_FN_GROUP + x];
-                const unsigned grid = gs.slab == 0 ? row_grid(cap) : (unsigned)blocks;
-                const hipError_t le =
-                    hipModuleLaunchKernel(fn, grid, 1, 1, 64 * wpb, 1, 1, (unsigned)lds, st, args, nullptr);
-                if (le != hipSuccess) {
-                    note_hip_error(le);
-                    return SPEC_E_HIP;
-                }
-            } else {
-                hipLaunchKernelGGL(tree_group_kernel, dim3((unsigned)blocks), dim3(64 * wpb), lds, st, Dd, Bd, x, gs.slab,
-                                   gs.wave_bytes, gs.rpw);
-            }
-        }
-        // every list owned in the level's groups: one batched scan per owner group
-        for (uint32_t x = 0; x < L.nt; x++) {
-            if (D.t[x].groot != x || lv[x] != level || !ms[x].n) continue;
-            const uint64_t cap = x == 0 ? n : d->caps[x];
-            if (cap == 0) continue;
-            const ListSet &m = ms[x];
-            const uint64_t tiles = std::max<uint64_t>(1, (cap + SCAN_TILE - 1) / SCAN_TILE);
-            hipLaunchKernelGGL(list_tiles_kernel, dim3((unsigned)tiles, m.n), dim3(SCAN_T), 0, st, Dd, Bd, m);
-            if (m.top) hipLaunchKernelGGL(list_top_kernel, dim3(m.n), dim3(SCAN_T), 0, st, Dd, Bd, m);
-            hipLaunchKernelGGL(list_apply_kernel, dim3((unsigned)tiles, m.n), dim3(SCAN_T), 0, st, Dd, Bd, m);
-        }
+        if (!launch_fused_set(c, plan, level, in_set)) return SPEC_E_HIP;
+        for (uint32_t x = 0; x < L.nt; x++)
+            if (plan.lv[x] == level && !in_set[x] && !launch_group(c, x)) return SPEC_E_HIP;
+        for (uint32_t x = 0; x < L.nt; x++)
+            if (plan.lv[x] == level) launch_list_scans(c, plan.lists[x]);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        note_hip_error(e);
-        return SPEC_E_HIP;
-    }
-    return SPEC_OK;
+    const hipError_t e = hipGetLastError(); // the run-time kernels' and the scans' launches
+    note_hip_error(e);
+    return e == hipSuccess ? SPEC_OK : SPEC_E_HIP;
 }
 
 // index: a decode without columns, then the row counts on the host; list capacities grow and
@@ -656,12 +639,8 @@ int spec_tree_decoder_reserve(spec_tree_decoder *d, const uint64_t *rows) {
 }
 
 long long spec_tree_jit_compile(const spec_tree *tree) {
-    Layout *L = new (std::nothrow) Layout();
-    if (!L) return SPEC_E_INVALID_ARGUMENT;
-    long long r = SPEC_E_INVALID_ARGUMENT;
-    if (build_layout(tree, *L)) r = jit_compile_only_tree(L->desc);
-    delete L;
-    return r;
+    const std::unique_ptr<Layout> L = make_layout(tree);
+    return L ? jit_compile_only_tree(L->desc) : SPEC_E_INVALID_ARGUMENT;
 }
 
 int spec_decode_values(int kind, const uint8_t *stream_bytes, uint64_t stream_len, const spec_span *spans, uint64_t n,

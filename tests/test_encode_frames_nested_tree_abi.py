@@ -134,6 +134,37 @@ def test_tree_argument_checks_without_gpu():
     assert call(tc, cols, rows, P, ws - 1) == WORKSPACE
 
 
+def test_tree_return_code_precedence_without_gpu():
+    # spec_encode_tree's checks in their order: invalid tree, workspace, then columns and rows
+    from spec_amd.tree import INPUT_ROLES, REL_ONE, Message, Tree
+
+    L = spec_amd.lib()
+    tree = Tree(Message("R", [("a", 1, Kind.INT32), ("sub", 2, Message("S", [("x", 1, Kind.INT64)]))]))
+    child = next(t for t in tree.tables if t.rel == REL_ONE)
+    nt, nc = len(tree.tables), len(tree.columns)
+    rows = (C.c_uint64 * nt)(*([8] * nt))
+    ws = L.spec_encode_tree_workspace_size(C.byref(tree.c), rows)
+    assert ws > 0
+
+    def call(tc, cp, rp, ws_size):
+        return L.spec_encode_tree(tc, cp, None, None, rp, P, 1 << 20, P, P, ws_size, P, None)
+
+    # a sub-message table has a row per owner row
+    short = (C.c_uint64 * nt)(*([8] * nt))
+    short[child.index] = 7
+    assert short[child.index] != short[child.parent]
+    assert call(C.byref(tree.c), _ptrs(nc), short, ws) == INVALID_ARGUMENT
+    # a null input column and a workspace one byte short: the workspace is checked first
+    hole = _ptrs(nc)
+    hole[next(c for c in tree.columns if c.role in INPUT_ROLES).index] = None
+    assert call(C.byref(tree.c), hole, rows, ws) == INVALID_ARGUMENT
+    assert call(C.byref(tree.c), hole, rows, ws - 1) == WORKSPACE
+    # an invalid tree and a workspace one byte short: the tree is checked first
+    bad = SpecTree.from_buffer_copy(tree.c)
+    bad.fields[0].parent = 5
+    assert call(C.byref(bad), _ptrs(nc), rows, ws - 1) == INVALID_ARGUMENT
+
+
 def test_generated_nested_encode_source_compiles_for_gfx950():
     # hiprtc, no device: the module of the size kernel, the write kernels (one wave per group and a
     # wave pair) and their framed instantiations

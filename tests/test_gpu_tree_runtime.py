@@ -31,7 +31,7 @@ from tests.test_gpu_tree import _fuzz, _root_windows, _spec_tree, to_dev
 from tests.test_tree import _test_object_columns
 from tests.tree_helpers import (mismatches, nested_struct_tree, oracle_decode, oracle_encode, roundtrip_mismatches,
                                 shapes_tree)
-from tests.trees import cross_kind_tree, many_tables_tree, wide_tree
+from tests.trees import cross_kind_tree, levels_tree, many_tables_tree, wide_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +84,8 @@ BATCHES = {
     "wide_n300": lambda: (wide_tree(), 300, dict(seed=800, count=(0, 3))),
     "many_tables_n1": lambda: (many_tables_tree(), 1, dict(seed=701, count=(0, 3))),
     "many_tables_n300": lambda: (many_tables_tree(), 300, dict(seed=1000, count=(0, 3))),
+    "levels_n257": lambda: (levels_tree(), 257, dict(seed=257)),
+    "levels_no_lists": lambda: (levels_tree(), 257, dict(seed=257, count=(0, 0))),
     **{f"spec_{name}": (lambda name=name: (_spec_tree(name), 300, dict(seed=77, count=(0, 3))))
        for name in ["pkg1.Message", "pmpx.Message", "prpc.Message", "pmpx.ChannelOpen"]},
 }
@@ -199,6 +201,50 @@ def test_empty_batch(dev, kernel):
     assert int(enc.encode(cols, {}, buf[64:64], ebuf[8:8]).item()) == 0
     torch.cuda.synchronize()
     assert (buf.cpu().numpy() == CANARY).all() and (ebuf.cpu().numpy() == ECANARY).all()
+
+
+def test_one_decoder_over_full_empty_and_listless_batches(dev, kernel):
+    """One TreeDecoder through batches in turn: 257 records of levels_tree (a 256-thread block and
+    one row; two tables at one height and at one depth), no records, the same records with every
+    list empty, the first batch again.  Each pass is the oracle's: no row count or column carries
+    over from the pass before.  (An encode of no records: test_empty_batch.)"""
+    full, bare = batch("levels_n257"), batch("levels_no_lists")
+    tree, n = full.tree, full.n
+    lists = [t.index for t in tree.tables if t.rel == REL_MANY]
+    assert len(tree.tables) == 4 and len(lists) == 2 and min(full.rows) > 0
+    assert [bare.rows[x] for x in lists] == [0, 0]
+    check_encode_decode(full, dev)
+
+    def put(b):
+        s = torch.from_numpy(b.stream if b.stream.size else np.zeros(1, np.uint8)).to(dev)[: b.stream.size]
+        return s, torch.from_numpy(b.ends.view(np.int64)).to(dev)
+
+    d = TreeDecoder(tree)
+    s_full, e_full = put(full)
+    d.index(s_full, e_full)
+    cols = d.alloc(dev)
+
+    def run(s, e, want_rows, want):
+        for c in cols:
+            c.fill_(CANARY)
+        rows_out = d.run(s, e, cols)
+        torch.cuda.synchronize()
+        assert rows_out.cpu().tolist() == want_rows
+        got = [c[: tree.column_rows(tc, want_rows)].cpu().numpy() for c, tc in zip(cols, tree.columns)]
+        assert want is None or mismatches(tree, got, want) == []
+        return [c.cpu().numpy() for c in cols]
+
+    first = run(s_full, e_full, full.want_rows, full.want)
+    # no records: no scan runs, the device row counts are reset (run()'s memset of rowsd): every
+    # count 0, no column written
+    after = run(s_full[:0], e_full[:0], [0] * len(tree.tables), None)
+    assert all((a == CANARY).all() for a in after)
+    # every list empty: every group has capacity from the index above, so the zeros come from the
+    # scans; the list tables (and the sub-message table under the items) have no rows
+    assert bare.want_rows == [n, 0, 0, 0]
+    run(*put(bare), bare.want_rows, bare.want)
+    again = run(s_full, e_full, full.want_rows, full.want)
+    assert all(np.array_equal(a, b) for a, b in zip(first, again))
 
 
 def test_pkg1_root_staged_and_unstaged(dev, kernel):

@@ -88,10 +88,21 @@ def message1_tree() -> Tree:
                                      ("l", 4, ListOf(Kind.STRING))]))
 
 
+def levels_tree() -> Tree:
+    """Three levels — records, a list of messages, under each item a list of strings and a
+    sub-message — so that one height (the strings, the sub-message) and one depth (the same two)
+    have two tables each: the encoder's level-fused launches with more than one member.  The
+    decoder has one group per level (records; items with their sub-message; strings): a list
+    group below a list group (test_gpu_tree_runtime's decoder-reuse case)."""
+    sub = Message("Sub", [("k", 1, Kind.INT32)])
+    item = Message("Item", [("v", 1, Kind.INT64), ("names", 2, ListOf(Kind.STRING)), ("sub", 3, sub)])
+    return Tree(Message("Levels", [("id", 1, Kind.INT32), ("items", 2, ListOf(item))]))
+
+
 def extra_trees() -> dict:
     """{name: Tree} the GPU tests decode and encode beyond the product's own trees."""
     out = {"shapes": shapes_tree(), "nested_struct": nested_struct_tree(), "wide": wide_tree(),
-           "many_tables": many_tables_tree(), "message1": message1_tree()}
+           "many_tables": many_tables_tree(), "message1": message1_tree(), "levels": levels_tree()}
     for shift in (1, 4, 9):
         out[f"cross_kind{shift}"] = cross_kind_tree(shift)
     return out
