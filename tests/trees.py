@@ -99,10 +99,17 @@ def levels_tree() -> Tree:
     return Tree(Message("Levels", [("id", 1, Kind.INT32), ("items", 2, ListOf(item))]))
 
 
+def any_first_tree() -> Tree:
+    """An `any` field written first: its slot (the message's data up to the field's end,
+    internal/types/msg.go:108-124) holds its own bytes and nothing else, so a value's class is the
+    catalog's (tests/any_values.py)."""
+    return Tree(Message("AnyFirst", [("any", 1, Kind.ANY), ("k", 2, Kind.INT32), ("s", 3, Kind.STRING)]))
+
+
 def extra_trees() -> dict:
     """{name: Tree} the GPU tests decode and encode beyond the product's own trees."""
     out = {"shapes": shapes_tree(), "nested_struct": nested_struct_tree(), "wide": wide_tree(),
-           "many_tables": many_tables_tree(), "message1": message1_tree(), "levels": levels_tree()}
+           "many_tables": many_tables_tree(), "message1": message1_tree(), "levels": levels_tree(), "any_first": any_first_tree()}
     for shift in (1, 4, 9):
         out[f"cross_kind{shift}"] = cross_kind_tree(shift)
     return out
