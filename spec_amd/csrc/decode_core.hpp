@@ -8,13 +8,14 @@
 // (internal/format/msg.go:227-265) + decode.Decode<Kind>(bytes[:end])).
 //
 // Mapping (MI355X, wave64):
-//   * one wave = 64 consecutive records, one record per lane;
-//   * the wave's contiguous byte span [ends[base-1], ends[base+63]) is staged into the wave's
+//   * one group = 64 consecutive records, one record per lane, on one wave (run-time schema) or
+//     on P waves that share the fields (generated kernels);
+//   * the group's contiguous byte span [ends[base-1], ends[base+63]) is staged into the group's
 //     private LDS slab with LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per instruction,
 //     range-checked by the buffer descriptor) — one fully coalesced HBM read of the stream;
 //   * each lane parses its record from LDS.  Two code paths:
 //       - the FAST path (schema known at compile time: `Spec` = a generated struct) reads the
-//         whole field table with a few wide LDS reads, checks that it holds exactly the
+//         field table with a few wide LDS reads, checks that it holds exactly the
 //         schema's tags in the order a Writer emits them (then the reference's binary search
 //         provably lands on the same entries), and decodes every field with straight-line,
 //         kind-specialised code the compiler can interleave (ILP across fields);
@@ -312,26 +313,15 @@ __device__ __forceinline__ Val decode_tail_k(const Win &w, Pos lo, Pos e, long l
     return out;
 }
 
-template <uint32_t KIND, class Src>
-__device__ __forceinline__ Val decode_value_k(const Src &s, typename Src::pos_t lo, typename Src::pos_t e,
-                                              long long to_stream) {
-    if ((long long)(e - lo) <= 0) return Val{0, 0, 0, 0}; // empty => zero value, no error
-    return decode_tail_k<KIND>(load_win<KIND>(s, e), lo, e, to_stream);
-}
-
+// Columns are written once and not read back by the kernel: non-temporal stores.
 template <class T>
 __device__ __forceinline__ void col_store(T *p, T v) {
-#if !defined(SPEC_CACHED_STORE)
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 template <uint32_t KIND>
 __device__ __forceinline__ void store_value_k(void *colp, uint64_t r, const Val &v) {
     uint8_t *col = (uint8_t *)colp;
-#if !defined(SPEC_CACHED_STORE)
     if constexpr (KIND == K_BOOL || KIND == K_BYTE) {
         col_store(col + r, (uint8_t)v.v0);
     } else if constexpr (KIND == K_INT16 || KIND == K_UINT16) {
@@ -348,23 +338,6 @@ __device__ __forceinline__ void store_value_k(void *colp, uint64_t r, const Val 
         col_store((uint64_t *)col + 4 * r + 3, v.v3);
     } else {
         col_store((uint64_t *)col + r, v.v0);
-    }
-    return;
-#endif
-    if constexpr (KIND == K_BOOL || KIND == K_BYTE) {
-        col[r] = (uint8_t)v.v0;
-    } else if constexpr (KIND == K_INT16 || KIND == K_UINT16) {
-        ((uint16_t *)col)[r] = (uint16_t)v.v0;
-    } else if constexpr (KIND == K_INT32 || KIND == K_UINT32 || KIND == K_FLOAT32) {
-        ((uint32_t *)col)[r] = (uint32_t)v.v0;
-    } else if constexpr (KIND == K_BIN128) {
-        ((ulonglong2 *)col)[r] = make_ulonglong2(v.v0, v.v1);
-    } else if constexpr (KIND == K_BIN256) {
-        ulonglong2 *c = (ulonglong2 *)col + 2 * r;
-        c[0] = make_ulonglong2(v.v0, v.v1);
-        c[1] = make_ulonglong2(v.v2, v.v3);
-    } else {
-        ((uint64_t *)col)[r] = v.v0;
     }
 }
 
@@ -579,23 +552,54 @@ __device__ __forceinline__ void decode_record_generic(const Src &s, typename Src
     if constexpr (PRESENT) fs.present[r] = pres;
 }
 
-// ---- fast path: compile-time schema ------------------------------------------------------
+// ---- fast paths: compile-time schema -----------------------------------------------------
+// Two of them, over the same Spec and the same value decoders:
+//   * register-resident (FastRec, FieldLoad / FieldNat / FieldStore, fast_prepare / fast_finish):
+//     the whole record's windows in registers, fields in schema order, list extents.  What the
+//     nested decode kernels run on outer records and items (decode_nested_core.hpp): small
+//     tables of at most FAST_MAX_FIELDS fields.
+//   * batched (WideField, wide_batch, fast_wide): the table walked FAST_BATCH entries at a time,
+//     fields in table order.  What every generated flat kernel runs (decode_flat_pair): any
+//     field count, small or big tables.
 
-// A run-time schema has no fast path.
+// A run-time schema has no fast path (the nested kernels' marker for "this level is generic").
 struct RuntimeSpec {
     static constexpr int N = 0;
     static constexpr bool big = false;
 };
 
 // Spec (generated by jit.cpp) provides:
-//   N              number of fields (1..SPEC_KFIELDS; the register-resident fast path below
-//                  takes up to FAST_MAX_FIELDS small-table fields, fast_wide the rest)
+//   N              number of fields (1..SPEC_KFIELDS)
 //   kind[f], rank[f]  per schema field
 //   stag[k]        k-th tag of the table a Writer emits (strictly increasing)
 //   order[k]       the schema field of table entry k (rank's inverse)
 //   big            the Writer's tables are big for every record (a tag > 255: IsBigMessage,
 //                  internal/format/msg.go:43-61)
+
+// Most fields of the register-resident path, and of the flat decode's ranked tables (fast_wide).
 constexpr int FAST_MAX_FIELDS = 24;
+
+// ---- reading table entries from the slab ---------------------------------------------------
+// A run of table entries starting at slab position p0, read with a few wide LDS reads and
+// re-aligned into qwords: c[j] = bytes [p0+8j, p0+8j+8), each a 64-bit funnel shift of two of the
+// NC + 1 aligned qwords covering the run.  (No select between array elements here: in the
+// not-yet-unrolled loop LLVM folds `hi ? d[i+1] : d[i]` into a load at a variable index, which
+// after unrolling is a 2N-deep v_cndmask chain per dword.)
+template <int NC>
+__device__ __forceinline__ void table_qwords(const LdsSrc &s, int p0, uint64_t (&c)[NC]) {
+    const int base = p0 & ~7;
+    const uint32_t sh = 8u * (uint32_t)(p0 & 7);
+    uint64_t q[NC + 1];
+#pragma unroll
+    for (int j = 0; j <= NC; j++) q[j] = s.d64(base + 8 * j);
+#pragma unroll
+    for (int j = 0; j < NC; j++) c[j] = (q[j] >> sh) | ((q[j + 1] << 1) << (63 - sh));
+}
+// (The callers pick the entries' bytes out of c[] themselves — a small table's entry is u8 tag |
+// u16 end, a big one's u16 tag | u32 end, internal/format/msg.go:138-186, big-endian: with that
+// loop in a function of its own the generated kernels come out scheduled differently.)
+
+// ---- the register-resident fast path (nested decode) --------------------------------------
 
 // Unrolled at compile time: field F's kind and table index are constants, so every field
 // is straight-line code.  Phase 1 issues every field's LDS reads, phase 2 decodes and
@@ -704,29 +708,14 @@ __device__ __forceinline__ bool fast_prepare_compact(const LdsSrc &s, int rs, in
 template <class Spec>
 __device__ __forceinline__ bool fast_prepare(const LdsSrc &s, int rs, int re, FastRec<Spec> &fr) {
     constexpr int N = Spec::N;
+    static_assert(!Spec::big, "small tables only");
     if (re <= rs) return false;
-#if !defined(SPEC_NO_COMPACT)
     if constexpr (3 * N + 4 <= 16) return fast_prepare_compact<Spec>(s, rs, re, fr);
-#endif
     Trailer tr = parse_trailer(s, rs, re);
     if ((tr.st != ST_OK) | tr.big | (tr.tsize != 3u * N)) return false;
-    const int ts = (int)tr.tstart;
-    // the table's 3N bytes, re-aligned into qwords: c[j] = bytes [ts+8j, ts+8j+8), each a
-    // 64-bit funnel shift of two aligned qwords.  (No select between array elements here: in
-    // the not-yet-unrolled loop LLVM folds `hi ? d[i+1] : d[i]` into a load at a variable
-    // index, which after unrolling is a 2N-deep v_cndmask chain per dword.)
-    constexpr int NC = (3 * N + 7) / 8;  // realigned qwords holding the table
-    constexpr int NQ = NC + 1;           // aligned qwords covering [ts & ~7, ts + 3N)
-    const int base = ts & ~7;
-    const uint32_t sh = 8u * (uint32_t)(ts & 7);
-    uint64_t q[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; j++) q[j] = s.d64(base + 8 * j);
-    uint64_t c[NC];
-#pragma unroll
-    for (int j = 0; j < NC; j++) c[j] = (q[j] >> sh) | ((q[j + 1] << 1) << (63 - sh));
-    // entry k = bytes 3k (tag), 3k+1..3k+2 (end, big-endian): the table must hold exactly the
-    // Writer's tags (strictly increasing), so binary search would land on entry rank[f]
+    // the table must hold exactly the Writer's tags, so binary search would land on entry rank[f]
+    uint64_t c[(3 * N + 7) / 8];
+    table_qwords(s, (int)tr.tstart, c);
     auto byte_at = [&](int j) -> uint32_t { return (uint32_t)(c[j >> 3] >> (8 * (j & 7))) & 0xff; };
     bool hit = true;
     uint32_t ends[N];
@@ -753,15 +742,14 @@ __device__ __forceinline__ void fast_finish(const FastRec<Spec> &fr, uint64_t r,
     if constexpr (ERR) fs.errmask[r] = errs;
 }
 
-// ---- fast path for wide schemas and big tables --------------------------------------------
-// Schemas with more than FAST_MAX_FIELDS fields, or whose tags make every table big (u16 tag |
-// u32 end entries, internal/format/msg.go:138-186).  The trailer is checked as by fast_prepare;
-// then the table is walked in batches of FAST_BATCH entries: the batch's entries read with a few
-// wide LDS reads and checked against the Writer's tags (strictly increasing, so the reference's
-// binary search lands on entry k for the k-th tag), its fields' windows read, their types checked
-// (the type a Writer emits for the kind), decoded and stored.  A record rejected after some
-// batches were stored runs the generic path, which rewrites every column and the status, so the
-// result never depends on where the fast path gave up.
+// ---- the batched fast path (flat decode) ----------------------------------------------------
+// Every generated flat kernel: any field count, small tables or (a tag > 255) big ones.  The
+// trailer is checked (table_accepted); then the table is walked in batches of FAST_BATCH entries:
+// the batch's end offsets are read (FullTable: the Writer's whole table, checked tag by tag;
+// RankedTable: a subset table, each entry at its popcount index), then the batch's fields'
+// windows are read, their types checked (the type a Writer emits for the kind), decoded and stored.
+// A record rejected after some batches were stored runs the generic path, which rewrites every
+// column and the status, so the result never depends on where the fast path gave up.
 constexpr int FAST_BATCH = 8;
 
 template <class Spec, int J0, int K, int NB>
@@ -808,54 +796,22 @@ struct RecMasks {
     uint64_t errs = 0, pres = 0;
 };
 
-// table entries [J0, J1): false when the record needs the generic path
-// PRESENT: the table holds every tag, so HasField(tag) is "its end lies within the data".
-template <class Spec, int J0, int J1, bool ERR, bool PRESENT = false>
-__device__ __forceinline__ bool wide_batch(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                           const FieldSet &fs, long long to_stream, RecMasks &m) {
-    constexpr int NB = J1 - J0;
-    constexpr int ESZ = Spec::big ? 6 : 3;
-    constexpr int NC = (ESZ * NB + 7) / 8, NQ = NC + 1;
-    const int p0 = ts + ESZ * J0;
-    const int base = p0 & ~7;
-    const uint32_t sh = 8u * (uint32_t)(p0 & 7);
-    uint64_t q[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; j++) q[j] = s.d64(base + 8 * j);
-    uint64_t c[NC];
-#pragma unroll
-    for (int j = 0; j < NC; j++) c[j] = (q[j] >> sh) | ((q[j + 1] << 1) << (63 - sh));
-    auto byte_at = [&](int j) -> uint32_t { return (uint32_t)(c[j >> 3] >> (8 * (j & 7))) & 0xff; };
-    bool hit = true;
-    uint32_t ends[NB];
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        if constexpr (Spec::big) {
-            hit = hit & (((byte_at(6 * k) << 8) | byte_at(6 * k + 1)) == Spec::stag[J0 + k]);
-            ends[k] = (byte_at(6 * k + 2) << 24) | (byte_at(6 * k + 3) << 16) | (byte_at(6 * k + 4) << 8) |
-                      byte_at(6 * k + 5);
-        } else {
-            hit = hit & (byte_at(3 * k) == Spec::stag[J0 + k]);
-            ends[k] = (byte_at(3 * k + 1) << 8) | byte_at(3 * k + 2);
-        }
-    }
-    if (!hit) return false;
-    if constexpr (PRESENT) {
-#pragma unroll
-        for (int k = 0; k < NB; k++) m.pres |= ends[k] <= dsize ? 1ull << Spec::order[J0 + k] : 0ull;
-    }
-    Win w[NB];
-    int e[NB], lo[NB];
-    WideField<Spec, J0, 0, NB>::load(w, e, lo, s, ds, ends, dsize);
-    if (!WideField<Spec, J0, 0, NB>::nat(w, e, lo)) return false;
-    WideField<Spec, J0, 0, NB>::template store<ERR>(w, e, lo, to_stream, fs, r, m.errs);
-    return true;
-}
-
-// ---- sparse records on the fast path (the PRESENT kernels, small tables) ------------------
-// A Writer that skipped some setters leaves a table of k <= N entries whose tags are a strictly
-// increasing subset of the schema's, so the reference's binary search finds exactly those tags
-// and the entry of the tag of rank j sits at index popcount(ranks present below j).
+// Which table a record's batches are read from (wide_batch has the two readers):
+// FullTable: the Writer's whole table (table_accepted's full form), rank k is entry k.  PRESENT:
+// the kernel collects HasField bits.
+template <bool PRESENT>
+struct FullTable {
+    static constexpr bool ranked = false, present = PRESENT;
+};
+// RankedTable: a small table of k <= N entries (table_accepted's sparse form; PRESENT kernels).  A
+// Writer that skipped some setters leaves a table whose tags are a strictly increasing subset of
+// the schema's, so the reference's binary search finds exactly those tags and the entry of the tag
+// of rank j sits at index popcount(ranks present below j).  ranks: the ranks the table holds
+// (present_ranks).
+struct RankedTable {
+    static constexpr bool ranked = true;
+    uint32_t ranks;
+};
 
 // The tags of a schema's Writer table as a 256-bit set (tags <= 255), one word per 64 tags.
 template <class Spec>
@@ -903,21 +859,49 @@ __device__ __forceinline__ bool present_ranks(const LdsSrc &s, int ts, uint32_t 
     return ok;
 }
 
-// Ranks [J0, J1) of a record whose table holds the ranks in `ranks`: each field's ONE entry read
-// from the slab at its popcount index (an absent field reads an entry or the trailer behind the
-// table and drops it), then window, type check, decode and store as wide_batch.
-template <class Spec, int J0, int J1, bool ERR>
-__device__ __forceinline__ bool present_batch(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint32_t ranks,
-                                              uint64_t r, const FieldSet &fs, long long to_stream, RecMasks &m) {
+// Table ranks [J0, J1) of one record: their end offsets from the table t at ts, the fields'
+// windows, type check, decode and store.  false when the record needs the generic path.  m gets the
+// batch's error-mask bits (ERR) and HasField bits.
+template <class Spec, int J0, int J1, bool ERR, class Table>
+__device__ __forceinline__ bool wide_batch(const LdsSrc &s, const Table &t, int ts, int ds, uint32_t dsize, uint64_t r,
+                                           const FieldSet &fs, long long to_stream, RecMasks &m) {
     constexpr int NB = J1 - J0;
     uint32_t ends[NB];
+    if constexpr (Table::ranked) {
+        // each field's ONE entry read from the slab at its popcount index (an absent field reads an
+        // entry or the trailer behind the table and drops it)
 #pragma unroll
-    for (int k = 0; k < NB; k++) {
-        const int p = ts + 3 * (int)__builtin_popcount(ranks & ((1u << (J0 + k)) - 1u));
-        const uint32_t end = (s.u8(p + 1) << 8) | s.u8(p + 2);
-        const bool has = ((ranks >> (J0 + k)) & 1) != 0;
-        ends[k] = has ? end : ~0u; // (~0 > dsize: absent to WideField::load as to m.field)
-        m.pres |= (has & (end <= dsize)) ? 1ull << Spec::order[J0 + k] : 0ull;
+        for (int k = 0; k < NB; k++) {
+            const int p = ts + 3 * (int)__builtin_popcount(t.ranks & ((1u << (J0 + k)) - 1u));
+            const uint32_t end = (s.u8(p + 1) << 8) | s.u8(p + 2);
+            const bool has = ((t.ranks >> (J0 + k)) & 1) != 0;
+            ends[k] = has ? end : ~0u; // (~0 > dsize: absent to WideField::load as to m.field)
+            m.pres |= (has & (end <= dsize)) ? 1ull << Spec::order[J0 + k] : 0ull;
+        }
+    } else {
+        // the batch's entries, checked tag by tag; the table holds every tag, so HasField(tag) is
+        // "its end lies within the data"
+        constexpr int ESZ = Spec::big ? 6 : 3;
+        uint64_t c[(ESZ * NB + 7) / 8];
+        table_qwords(s, ts + ESZ * J0, c);
+        auto byte_at = [&](int j) -> uint32_t { return (uint32_t)(c[j >> 3] >> (8 * (j & 7))) & 0xff; };
+        bool hit = true;
+#pragma unroll
+        for (int k = 0; k < NB; k++) {
+            if constexpr (Spec::big) {
+                hit = hit & (((byte_at(6 * k) << 8) | byte_at(6 * k + 1)) == Spec::stag[J0 + k]);
+                ends[k] = (byte_at(6 * k + 2) << 24) | (byte_at(6 * k + 3) << 16) | (byte_at(6 * k + 4) << 8) |
+                          byte_at(6 * k + 5);
+            } else {
+                hit = hit & (byte_at(3 * k) == Spec::stag[J0 + k]);
+                ends[k] = (byte_at(3 * k + 1) << 8) | byte_at(3 * k + 2);
+            }
+        }
+        if (!hit) return false;
+        if constexpr (Table::present) {
+#pragma unroll
+            for (int k = 0; k < NB; k++) m.pres |= ends[k] <= dsize ? 1ull << Spec::order[J0 + k] : 0ull;
+        }
     }
     Win w[NB];
     int e[NB], lo[NB];
@@ -927,53 +911,24 @@ __device__ __forceinline__ bool present_batch(const LdsSrc &s, int ts, int ds, u
     return true;
 }
 
+// table ranks [J0, JE) in batches of FAST_BATCH (one wave's part of a record)
 template <class Spec, int J0, int JE, bool ERR>
-struct PresentBatchesTo {
-    static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint32_t ranks,
+struct WideBatchesTo {
+    template <class Table>
+    static __device__ __forceinline__ bool run(const LdsSrc &s, const Table &t, int ts, int ds, uint32_t dsize,
                                                uint64_t r, const FieldSet &fs, long long to_stream, RecMasks &m) {
         if constexpr (J0 >= JE) {
             return true;
         } else {
             constexpr int J1 = J0 + FAST_BATCH < JE ? J0 + FAST_BATCH : JE;
-            if (!present_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, ranks, r, fs, to_stream, m)) return false;
-            return PresentBatchesTo<Spec, J1, JE, ERR>::run(s, ts, ds, dsize, ranks, r, fs, to_stream, m);
+            if (!wide_batch<Spec, J0, J1, ERR>(s, t, ts, ds, dsize, r, fs, to_stream, m)) return false;
+            return WideBatchesTo<Spec, J1, JE, ERR>::run(s, t, ts, ds, dsize, r, fs, to_stream, m);
         }
     }
 };
 
-template <class Spec, int J0, bool ERR>
-struct WideBatches {
-    static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                               const FieldSet &fs, long long to_stream, RecMasks &m) {
-        if constexpr (J0 >= Spec::N) {
-            return true;
-        } else {
-            constexpr int J1 = J0 + FAST_BATCH < Spec::N ? J0 + FAST_BATCH : Spec::N;
-            if (!wide_batch<Spec, J0, J1, ERR>(s, ts, ds, dsize, r, fs, to_stream, m)) return false;
-            return WideBatches<Spec, J1, ERR>::run(s, ts, ds, dsize, r, fs, to_stream, m);
-        }
-    }
-};
-
-// table entries [J0, JE) in batches of FAST_BATCH (a wave pair's half of a wide record)
-template <class Spec, int J0, int JE, bool ERR = false, bool PRESENT = false>
-struct WideBatchesTo {
-    static __device__ __forceinline__ bool run(const LdsSrc &s, int ts, int ds, uint32_t dsize, uint64_t r,
-                                               const FieldSet &fs, long long to_stream, RecMasks &m) {
-        if constexpr (J0 >= JE) {
-            return true;
-        } else {
-            constexpr int J1 = J0 + FAST_BATCH < JE ? J0 + FAST_BATCH : JE;
-            if (!wide_batch<Spec, J0, J1, ERR, PRESENT>(s, ts, ds, dsize, r, fs, to_stream, m)) return false;
-            return WideBatchesTo<Spec, J1, JE, ERR, PRESENT>::run(s, ts, ds, dsize, r, fs, to_stream, m);
-        }
-    }
-};
-
-// Part h of P of a record's fields (table entries [lo(h), lo(h + 1)); for a pair the boundary is
-// the batch boundary near N/2) for the waves of one group (decode_flat_pair): false when this part
-// needs the generic path.  No status: the group's first wave writes it once every part succeeded.
-// ERR: this part's error-mask bits in errs.
+// Part h of P of a record's fields: table ranks [lo(h), lo(h + 1)); for a pair the boundary is
+// the batch boundary near N/2.
 template <class Spec, int P>
 __host__ __device__ constexpr int flat_part_lo(int h) {
     if (h >= P) return Spec::N;
@@ -985,72 +940,58 @@ __host__ __device__ constexpr int flat_part_lo(int h) {
     }
     return (h * Spec::N) / P;
 }
-template <class Spec, bool ERR, int P, bool PRESENT = false, int H = 0>
-__device__ __forceinline__ bool wide_part_run(const LdsSrc &s, const Trailer &tr, uint64_t r, const FieldSet &fs,
-                                              long long to_stream, int h, RecMasks &m) {
+// part h (wave-uniform, run-time) -> its compile-time range of ranks
+template <class Spec, bool ERR, int P, class Table, int H = 0>
+__device__ __forceinline__ bool wide_part_run(const LdsSrc &s, const Table &t, const Trailer &tr, uint64_t r,
+                                              const FieldSet &fs, long long to_stream, int h, RecMasks &m) {
     if constexpr (H >= P) {
         return true;
     } else {
         constexpr int J0 = flat_part_lo<Spec, P>(H), J1 = flat_part_lo<Spec, P>(H + 1);
         if (h == H)
-            return WideBatchesTo<Spec, J0, J1, ERR, PRESENT>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs,
-                                                                  to_stream, m);
-        return wide_part_run<Spec, ERR, P, PRESENT, H + 1>(s, tr, r, fs, to_stream, h, m);
+            return WideBatchesTo<Spec, J0, J1, ERR>::run(s, t, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs,
+                                                         to_stream, m);
+        return wide_part_run<Spec, ERR, P, Table, H + 1>(s, t, tr, r, fs, to_stream, h, m);
     }
 }
+
+// The two trailers the batched fast path takes; every other record runs the generic path.
+//   full:   the table is of the size and entry width of the Writer's whole table (wide_batch then
+//           checks its tags);
+//   sparse: a small table of at most N entries (present_ranks then checks its tags).
+// (Written as "none of the reasons to reject": the conjunction of the positive tests compiles to
+// other code.)
+template <class Spec, bool SPARSE>
+__device__ __forceinline__ bool table_accepted(const Trailer &tr) {
+    if constexpr (SPARSE)
+        return !((tr.st != ST_OK) | tr.big | (tr.tsize > 3u * (uint32_t)Spec::N));
+    else
+        return !((tr.st != ST_OK) | (tr.big != Spec::big) | (tr.tsize != (Spec::big ? 6u : 3u) * (uint32_t)Spec::N));
+}
+
+// Part h of P of record r (slab positions [rs, re)) for wave h of the record's group
+// (decode_flat_pair): false when this part needs the generic path.  No status: the group's first
+// wave writes it once every part succeeded.  m gets this part's error-mask bits (ERR) and HasField
+// bits.
+// A PRESENT kernel of a small-table schema of at most FAST_MAX_FIELDS fields takes the sparse form
+// (the full table included): every wave of the group reads the whole tag column, since it needs
+// the ranks below its own part.  Every other kernel takes the full form; a PRESENT kernel of a
+// wide or big-table schema so sends a subset table to the generic path.
 template <class Spec, bool ERR = false, int P = 2, bool PRESENT = false>
-__device__ __forceinline__ bool fast_wide_half(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
-                                               long long to_stream, int h, RecMasks &m) {
+__device__ __forceinline__ bool fast_wide(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
+                                          long long to_stream, int h, RecMasks &m) {
+    constexpr bool SPARSE = PRESENT && Spec::N <= FAST_MAX_FIELDS && !Spec::big;
     if (re <= rs) return false;
     const Trailer tr = parse_trailer(s, rs, re);
-    if ((tr.st != ST_OK) | (tr.big != Spec::big) | (tr.tsize != (Spec::big ? 6u : 3u) * (uint32_t)Spec::N)) return false;
-    return wide_part_run<Spec, ERR, P, PRESENT>(s, tr, r, fs, to_stream, h, m);
-}
-
-// The PRESENT kernels' part h of a record of a small-table schema of at most FAST_MAX_FIELDS
-// fields: any table of k <= N entries that present_ranks accepts (the full table included), the
-// ranks of this part through present_batch.  Every wave of the group reads the whole tag column
-// (it needs the ranks below its own part); m.pres gets this part's HasField bits.
-template <class Spec, bool ERR, int P, int H = 0>
-__device__ __forceinline__ bool present_part_run(const LdsSrc &s, const Trailer &tr, uint32_t ranks, uint64_t r,
-                                                 const FieldSet &fs, long long to_stream, int h, RecMasks &m) {
-    if constexpr (H >= P) {
-        return true;
+    if (!table_accepted<Spec, SPARSE>(tr)) return false;
+    if constexpr (SPARSE) {
+        RankedTable t;
+        if (!present_ranks<Spec>(s, (int)tr.tstart, tr.tsize / 3u, t.ranks)) return false;
+        return wide_part_run<Spec, ERR, P>(s, t, tr, r, fs, to_stream, h, m);
     } else {
-        constexpr int J0 = flat_part_lo<Spec, P>(H), J1 = flat_part_lo<Spec, P>(H + 1);
-        if (h == H)
-            return PresentBatchesTo<Spec, J0, J1, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, ranks, r, fs,
-                                                            to_stream, m);
-        return present_part_run<Spec, ERR, P, H + 1>(s, tr, ranks, r, fs, to_stream, h, m);
+        return wide_part_run<Spec, ERR, P>(s, FullTable<PRESENT>{}, tr, r, fs, to_stream, h, m);
     }
 }
-template <class Spec, bool ERR = false, int P = 2>
-__device__ __forceinline__ bool fast_present_half(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
-                                                  long long to_stream, int h, RecMasks &m) {
-    if (re <= rs) return false;
-    const Trailer tr = parse_trailer(s, rs, re);
-    if ((tr.st != ST_OK) | tr.big | (tr.tsize > 3u * (uint32_t)Spec::N)) return false;
-    uint32_t ranks;
-    if (!present_ranks<Spec>(s, (int)tr.tstart, tr.tsize / 3u, ranks)) return false;
-    return present_part_run<Spec, ERR, P>(s, tr, ranks, r, fs, to_stream, h, m);
-}
-
-// The whole record (columns, status, errmask); false: nothing final written, run the generic path.
-template <class Spec, bool ERR = false>
-__device__ __forceinline__ bool fast_wide(const LdsSrc &s, int rs, int re, uint64_t r, const FieldSet &fs,
-                                          long long to_stream) {
-    if (re <= rs) return false;
-    const Trailer tr = parse_trailer(s, rs, re);
-    if ((tr.st != ST_OK) | (tr.big != Spec::big) | (tr.tsize != (Spec::big ? 6u : 3u) * (uint32_t)Spec::N)) return false;
-    RecMasks m;
-    if (!WideBatches<Spec, 0, ERR>::run(s, (int)tr.tstart, (int)tr.dstart, tr.dsize, r, fs, to_stream, m))
-        return false;
-    if (fs.status) fs.status[r] = ST_OK;
-    if constexpr (ERR) fs.errmask[r] = m.errs;
-    return true;
-}
-
-// ---- kernel body -------------------------------------------------------------------------
 
 // ---- staging a span of the stream into LDS -------------------------------------------------
 // One primitive for every kernel that parses from LDS (flat, nested, validate, tree rows): a
@@ -1161,85 +1102,86 @@ __device__ __forceinline__ Group make_group(uint64_t n, uint64_t base, uint64_t 
     gr.in_lds = slab > 0 && l0 <= last && span_hi >= span_lo && SLAB_GUARD + (uint64_t)gr.st.bytes() + 16 <= (uint64_t)slab;
     return gr;
 }
-__device__ __forceinline__ Group make_group(const DecodeArgs &a, uint64_t base, int lane, uint64_t lo, uint64_t hi,
-                                            uint32_t slab) {
-    return make_group(a.n, base, lo, hi, slab);
-}
 
-// One group per wave: stage, decode, done.  ERR: the variant that also writes the per-record
-// field error masks (a.f.errmask, spec_decode_flat_errors).  PRESENT (run-time schemas only): the
-// generic path with the HasField masks (a.f.present, spec_decode_flat_present).
-template <class Spec, bool ERR = false, bool PRESENT = false>
-__device__ __forceinline__ void decode_flat_once(const DecodeArgs &a) {
-    static_assert(!PRESENT || Spec::N == 0, "the schema-specialised PRESENT kernel is decode_flat_pair");
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int wave = threadIdx.x >> 6;
-    const int lane = threadIdx.x & 63;
-    // blocks are dealt round-robin to the 8 XCDs: with xcd = 1, block b takes the b/8-th slot
-    // of XCD b%8's contiguous share of the groups, so neighbouring groups (which share the
-    // narrow columns' cache lines) are written through one L2
+// ---- the flat decode's kernel bodies ---------------------------------------------------------
+// Which path a schema's records take, by the kernel that decodes them:
+//   run-time schema (decode_flat.hip: decode_flat_kernel, decode_flat_present_kernel; every
+//   schema with the generated kernels switched off)
+//       decode_flat_runtime: a group per wave -> decode_record_generic for every record;
+//   generated, plain or _err (jit.cpp: spec_decode_flat[_wide][_err]_pair_jit), and generated
+//   _present of a schema of more than FAST_MAX_FIELDS fields or with a tag > 255
+//       decode_flat_pair: a group per P waves -> fast_wide, full form (FullTable);
+//   generated _present, small tables, at most FAST_MAX_FIELDS fields
+//       decode_flat_pair -> fast_wide, sparse form (present_ranks, RankedTable);
+//   and under every generated kernel: a record fast_wide rejects, or a group whose span does
+//   not fit the slab -> decode_record_generic.
+
+// Block b's place among the grid's blocks.  Blocks are dealt round-robin to the 8 XCDs: with
+// a.xcd = 1, block b takes the b/8-th slot of XCD b%8's contiguous share, so neighbouring groups
+// (which share the narrow columns' cache lines) are written through one L2.
+__device__ __forceinline__ uint64_t flat_block(const DecodeArgs &a) {
     uint64_t blk = blockIdx.x;
     if (a.xcd) {
         const uint64_t per = (gridDim.x + 7) / 8;
         blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     }
+    return blk;
+}
+
+// Opens the group of the 64 records from base (< a.n): this lane's record bounds from ends[] (one
+// load per lane, the lower bound from the lane below) and the group's span.
+__device__ __forceinline__ Group open_group(const DecodeArgs &a, uint64_t base, int lane) {
+    const uint64_t r = base + lane;
+    const uint64_t hi = a.ends[r < a.n ? r : a.n - 1];
+    uint64_t lo = __shfl_up(hi, 1);
+    if (lane == 0) lo = r == 0 ? 0 : a.ends[r - 1];
+    lo += a.head;
+    return make_group(a.n, base, lo, hi, a.slab);
+}
+
+// Run-time schema: one group per wave (blockDim / 64 groups per block): stage, decode every
+// record on the generic path, done.  It writes a.f.errmask when that is set
+// (spec_decode_flat_errors).  PRESENT: with the HasField masks (a.f.present,
+// spec_decode_flat_present).
+template <bool PRESENT = false>
+__device__ __forceinline__ void decode_flat_runtime(const DecodeArgs &a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const uint64_t blk = flat_block(a);
     const uint64_t base = a.r0 + (blk * (blockDim.x >> 6) + wave) * 64;
     if (base >= a.n) return;
     const uint64_t r = base + lane;
     const bool valid = r < a.n;
     uint8_t *slab = smem + wave * a.slab;
-    __amdgpu_buffer_rsrc_t rsrc =
-        uniform_rsrc(a.stream, a.stream_len);
-    const uint64_t hi = a.ends[valid ? r : a.n - 1];
-    uint64_t lo = __shfl_up(hi, 1);
-    if (lane == 0) lo = r == 0 ? 0 : a.ends[r - 1];
-    lo += a.head;
-    const Group cur = make_group(a, base, lane, lo, hi, a.slab);
+    __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(a.stream, a.stream_len);
+    const Group cur = open_group(a, base, lane);
     if (cur.in_lds) {
         stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, cur.st, a.stream_len, lane);
         if (!valid) return;
         LdsSrc s{(lds_u8 *)slab};
-        const int rs = cur.rs(), re = cur.re();
-        const long long to_stream = cur.to_stream();
-        if constexpr (Spec::N > 0) {
-            if constexpr (Spec::N <= FAST_MAX_FIELDS && !Spec::big) {
-                FastRec<Spec> fr;
-                if (fast_prepare<Spec>(s, rs, re, fr)) {
-                    fast_finish<Spec, ERR>(fr, r, a.f, to_stream);
-                    return;
-                }
-            } else {
-                if (fast_wide<Spec, ERR>(s, rs, re, r, a.f, to_stream)) return;
-            }
-        }
-        decode_record_generic<PRESENT>(s, rs, re, r, a.f, to_stream);
+        decode_record_generic<PRESENT>(s, cur.rs(), cur.re(), r, a.f, cur.to_stream());
     } else if (valid) {
         GlobalSrc s{a.stream, a.stream_len};
         decode_record_generic<PRESENT>(s, (long long)cur.rec_lo, (long long)cur.rec_hi, r, a.f, 0);
     }
 }
 
-// A wide schema's group of 64 records on a wave PAIR (a 128-thread block): both waves stage the
-// group's span once in the block's slab (each issues half the LDS-DMA chunks), each decodes half
-// of the fields (fast_wide_half), wave 1 hands its verdict to wave 0 through LDS, and wave 0
+// Generated kernels: a group of 64 records on a wave PAIR (a 128-thread block): both waves stage
+// the group's span once in the block's slab (each issues half the LDS-DMA chunks), each decodes
+// half of the fields (fast_wide), wave 1 hands its verdict to wave 0 through LDS, and wave 0
 // writes the status — or, where either half needs it, runs the generic path over the whole
 // record (it rewrites every column).  Same LDS per 64 records, twice the waves: one wave's LDS
 // and memory latency overlaps the other's decode.  ERR: every wave's mask bits, OR-ed by wave 0.
 // P waves per group in general (P parts of the fields; jit.cpp FLAT_WAVES).
 // PRESENT: also the HasField masks (a.f.present, spec_decode_flat_present), every wave's bits OR-ed
-// by wave 0 like the error bits.  A small-table schema of at most FAST_MAX_FIELDS fields takes
-// sparse records on the fast path (fast_present_half); the other schemas take full tables there
-// and send a subset table to the generic path.
+// by wave 0 like the error bits.
 template <class Spec, bool ERR = false, int P = 2, bool PRESENT = false>
 __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int wave = threadIdx.x >> 6;
     const int lane = threadIdx.x & 63;
-    uint64_t blk = blockIdx.x;
-    if (a.xcd) {
-        const uint64_t per = (gridDim.x + 7) / 8;
-        blk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-    }
+    const uint64_t blk = flat_block(a);
     const uint64_t base = a.r0 + blk * 64;
     if (base >= a.n) return; // (block-uniform)
     const uint64_t r = base + lane;
@@ -1247,11 +1189,7 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     uint8_t *slab = smem;
     uint32_t *xch = (uint32_t *)(smem + a.slab);
     __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(a.stream, a.stream_len);
-    const uint64_t hi = a.ends[valid ? r : a.n - 1];
-    uint64_t lo = __shfl_up(hi, 1);
-    if (lane == 0) lo = r == 0 ? 0 : a.ends[r - 1];
-    lo += a.head;
-    const Group cur = make_group(a, base, lane, lo, hi, a.slab);
+    const Group cur = open_group(a, base, lane);
     if (!cur.in_lds) {
         if (wave == 0 && valid) {
             GlobalSrc s{a.stream, a.stream_len};
@@ -1265,11 +1203,7 @@ __device__ __forceinline__ void decode_flat_pair(const DecodeArgs &a) {
     const int rs = cur.rs(), re = cur.re();
     const long long to_stream = cur.to_stream();
     RecMasks mine;
-    bool ok;
-    if constexpr (PRESENT && Spec::N <= FAST_MAX_FIELDS && !Spec::big)
-        ok = valid && fast_present_half<Spec, ERR, P>(s, rs, re, r, a.f, to_stream, wave, mine);
-    else
-        ok = valid && fast_wide_half<Spec, ERR, P, PRESENT>(s, rs, re, r, a.f, to_stream, wave, mine);
+    const bool ok = valid && fast_wide<Spec, ERR, P, PRESENT>(s, rs, re, r, a.f, to_stream, wave, mine);
     // waves 1 .. P-1: verdicts at slab + 256 (w - 1), ERR: mask bits after them (512 B per wave),
     // PRESENT: HasField bits after those (512 B per wave)
     uint64_t *xerr = (uint64_t *)(xch + 64 * (P - 1));

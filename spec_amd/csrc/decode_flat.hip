@@ -8,12 +8,12 @@
 
 namespace spec {
 
-__global__ __launch_bounds__(256) void decode_flat_kernel(DecodeArgs a) { decode_flat_once<RuntimeSpec>(a); }
+__global__ __launch_bounds__(256) void decode_flat_kernel(DecodeArgs a) { decode_flat_runtime(a); }
 
 // spec_decode_flat_present / spec_decode_frames_present on a run-time schema: the same body with
 // the HasField masks (a.f.present)
 __global__ __launch_bounds__(256) void decode_flat_present_kernel(DecodeArgs a) {
-    decode_flat_once<RuntimeSpec, false, true>(a);
+    decode_flat_runtime<true>(a);
 }
 
 int device_cus() {
@@ -32,7 +32,7 @@ int launch_decode_flat(DecodeArgs a, double avg_record, hipStream_t stream) {
     if (a.n <= a.r0) return 0;
     const DecodeLaunch L = decode_launch(a.n - a.r0, avg_record);
     a.slab = L.slab;
-    a.xcd = 1; // XCD-aware contiguous shares of the groups (decode_core.hpp decode_flat_once)
+    a.xcd = 1; // XCD-aware contiguous shares of the groups (decode_core.hpp flat_block)
     if (a.f.present) hipLaunchKernelGGL(decode_flat_present_kernel, dim3(L.blocks), dim3(64), L.slab, stream, a);
     else hipLaunchKernelGGL(decode_flat_kernel, dim3(L.blocks), dim3(64), L.slab, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -1;

@@ -414,7 +414,7 @@ __device__ __forceinline__ void nested_decode_pair(const NestedArgs &a) {
     d.head = a.head;
     uint64_t lo, hi;
     load_group_ends(d, base, lane, lo, hi);
-    const Group gr = make_group(d, base, lane, lo, hi, a.slab);
+    const Group gr = make_group(a.n, base, lo, hi, a.slab);
     if (!gr.in_lds) {
         if (wave == 0) {
             const uint32_t first = nested_decode_part<OSpec, ISpec, false, U>(a, rsrc, slab, g, item_base, lane, 0, 32);

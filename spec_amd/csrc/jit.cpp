@@ -9,8 +9,9 @@
 // schema).  The generated kernel keeps the generic path for every record its fast path
 // rejects, so results are identical to the precompiled kernel's.
 //
-// Schemas without a fast path (more than FAST_MAX_FIELDS fields, repeated tags, tags >
-// 255) and SPEC_AMD_JIT=0 use the precompiled generic kernel (decode_flat.hip).
+// Every flat schema whose Writer table is strictly increasing has a generated kernel, whatever
+// its field count or tags (has_flat_fast_path).  A schema with repeated tags or a list field, and every schema
+// under SPEC_AMD_JIT=0, runs the precompiled run-time kernel (decode_flat.hip).
 //
 // Encode: the generated Write() (internal/lang/generator/message.go:319-439) likewise —
 // encode_core.hpp's size and write bodies over SpecEnc<schema> (every column load of a
@@ -51,10 +52,11 @@ bool schema_fits(const spec_schema *s, uint32_t max_fields, bool lists, uint32_t
     return true;
 }
 
-// The flat decoder's fast path (decode_core.hpp fast_prepare / fast_wide): any field count, tags
-// <= 255 (small tables) or with a tag > 255 (every table big).
+// The flat decoder's fast path (decode_core.hpp fast_wide, the batched path): any field count,
+// tags <= 255 (small tables) or with a tag > 255 (every table big), no list field.
 bool has_flat_fast_path(const spec_schema *s) { return schema_fits(s, SPEC_KFIELDS, false, 0xffff); }
-// The nested decoder's fast path (register-resident): tags <= 255, at most FAST_MAX_FIELDS fields.
+// The nested decoder's fast path (decode_core.hpp fast_prepare, register-resident), per level:
+// tags <= 255, at most FAST_MAX_FIELDS fields; a level without one is decoded generically.
 bool has_fast_path(const spec_schema *s) { return schema_fits(s, spec::FAST_MAX_FIELDS, true, 255); }
 // A schema-specialised encoder exists for 1..ENC_MAX_FIELDS fields without list fields.
 constexpr uint32_t ENC_MAX_FIELDS = 32;
@@ -98,7 +100,8 @@ void emit_spec(std::ostringstream &o, const char *name, const spec_schema *s) {
 // waves per 64-record group of the flat decode (decode_core.hpp decode_flat_pair)
 constexpr int FLAT_WAVES = 2;
 
-// schemas on decode_core.hpp fast_wide get kernels of their own names (traces tell them apart)
+// wide schemas and big tables get kernels of their own names (traces tell them apart); their
+// _present kernels read full tables only (decode_core.hpp fast_wide)
 bool flat_wide(const spec_schema *s) { return s->nfields > (uint32_t)spec::FAST_MAX_FIELDS || any_big_tag(s); }
 
 std::string generate_decode(const spec_schema *s) {

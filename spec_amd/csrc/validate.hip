@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void parse_kernel(DecodeArgs a, uint32_t *size
         uniform_rsrc(a.stream, a.stream_len);
     uint64_t lo, hi;
     load_group_ends(a, base, lane, lo, hi);
-    const Group gr = make_group(a, base, lane, lo, hi, a.slab);
+    const Group gr = make_group(a.n, base, lo, hi, a.slab);
     uint32_t st = ST_OK, size = 0;
     if (gr.in_lds) {
         stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);

@@ -245,7 +245,7 @@ def shape_sweep_schemas():
     n<N>[p]: N fields, tags 1..N, kinds cycling through the 15 flat kinds from (15 - N) mod 15 (a
     schema of fewer than 15 fields ends on STRING/BYTES), p: write order permuted (fixed seed).
       1, 2, 8, 9, 17, 18, 33, 34, 49, 63, 64   the decode wave pair's split (decode_core.hpp flat_part_lo)
-      24, 25                                    FAST_MAX_FIELDS: fast_present_half | fast_wide_half
+      24, 25                                    FAST_MAX_FIELDS: fast_wide's sparse | full form
       21, 22, 32, 33                            SpecEnc: register-built table | emit_table; the last
                                                 specialised encoder | the run-time one
     big21, big22: tags 250, 253, ... (a tag > 255: every table big; 6N = 126 | 132, a one- | two-byte

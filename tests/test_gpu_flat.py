@@ -454,6 +454,51 @@ def test_decode_range_and_host_pipeline(dev):
         assert np.array_equal(c3[13].numpy(), want[13][r0:r1]) and np.array_equal(s3.numpy(), wst[r0:r1])
 
 
+def test_runtime_kernel_errmask_and_present(dev):
+    """The precompiled run-time kernels (the generated ones switched off) through
+    spec_decode_flat_errors and spec_decode_flat_present with an errmask: 130 Flat16 records (two
+    full groups and a group of two lanes) holding a record with a truncated trailer, one whose int32
+    and int16 fields were written as wider types (their getters err) and an empty record — columns,
+    status, errmask and present against the oracle, and equal to the generated kernels' on the same
+    bytes."""
+    from tests.gpu_helpers import check_errors
+    from tests.present_helpers import check_present, decode_present_abi
+
+    n = 130
+    cols, heaps = workload.flat16(n, seed=31)
+    stream, ends = oracle_encode(FLAT16, cols, heaps, n)
+    recs = [bytes(stream[(int(ends[i - 1]) if i else 0):int(ends[i])]) for i in range(n)]
+    foreign = write_record([(3, Kind.INT32, 70000), (4, Kind.INT64, 1 << 40), (5, Kind.INT64, -3),
+                            (14, Kind.STRING, "s")])
+    recs[63] = recs[63][:-1]  # no type byte: the record does not open
+    recs[64] = foreign
+    recs[129] = b""
+    stream, ends = concat_records(recs)
+    want_bits = (1 << 2) | (1 << 3)  # int16 <- 70000, int32 <- 2^40: out of range
+    outs = {}
+    for jit in (False, True):
+        spec_amd.set_jit(jit)
+        try:
+            if jit:
+                require_specialised(FLAT16, "flat16", decode=(stream.size, n))
+            em = check_errors(dev, FLAT16, stream, ends, f"errors jit={jit}")
+            pm = check_present(dev, FLAT16, recs, f"present jit={jit}", errors=True)
+            outs[jit] = (em, decode_present_abi(dev, FLAT16, stream, ends, errors=True))
+        finally:
+            spec_amd.set_jit(True)
+        em = em.reshape(-1)
+        assert int(em[64]) == want_bits and int(em[63]) == 0 and int(em[129]) == 0
+        assert int(pm[0, 64]) == (1 << 2) | (1 << 3) | (1 << 4) | (1 << 13)
+        assert int(pm[0, 63]) == 0 and int(pm[0, 129]) == 0
+    (em0, (cols0, st0, pm0, pem0)), (em1, (cols1, st1, pm1, pem1)) = outs[False], outs[True]
+    assert st0[63] != 0 and st0[64] == 0
+    assert int(pem0[0, 64]) == want_bits
+    assert np.array_equal(em0, em1) and np.array_equal(st0, st1)
+    assert np.array_equal(pm0, pm1) and np.array_equal(pem0, pem1)
+    for f in range(len(FLAT16)):
+        assert np.array_equal(cols0[f], cols1[f]), f
+
+
 def test_decode_frames_in_place(dev, kernel):
     """mpx frames decoded in place == the same records decoded from a compact stream (spans
     shifted by the 4-byte heads before them)."""
