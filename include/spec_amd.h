@@ -58,7 +58,9 @@ extern "C" {
  *      spec_nested_schema.item at offset 4100, spec_tree 8196 B; spec_struct_size / _offset added;
  *      spec_lz4_state.reserved became content_checksum (same layout); spec_lz4_content added;
  *      later, with no struct changed: spec_lz4_frame_bound, spec_lz4_compress_workspace_size,
- *      spec_lz4_compress_frame and the SPEC_LZ4_OPEN / _CLOSE / _CONTENT_CHECKSUM flags. */
+ *      spec_lz4_compress_frame and the SPEC_LZ4_OPEN / _CLOSE / _CONTENT_CHECKSUM flags;
+ *      later, layout-compatible: spec_tree_field.reserved bit 0 = SPEC_TREE_FIELD_OPTIONAL (any other
+ *      bit is now refused) and the column role SPEC_COL_HASMASK. */
 #define SPEC_AMD_ABI_VERSION 2
 /* Fields of a flat schema.  Schemas of up to 64 fields run the schema-specialised kernels; wider
  * ones decode in chunks of 64 fields (the generic kernel once per chunk, each getter against the
@@ -191,13 +193,30 @@ typedef struct spec_nested_schema {
  *   <Kind>Err (msg.go:233-459), ANY OpenValueErr (value.go:35-46), MESSAGE MessageErr, LIST
  *   ListErr (msg.go:453-463), STRUCT DecodeXxx (generator/struct.go:60-64); an absent field never
  *   errs;
+ *   [HASMASK] uint64 x W (only MESSAGE-shaped tables with at least one SPEC_TREE_FIELD_OPTIONAL
+ *   direct field; same W and bit numbering as ERRMASK): bit k = m.HasField(tag of the k-th direct
+ *   field) on the row's opened message (msg.go:101-106), for EVERY direct field, flagged or not —
+ *   the bits of MESSAGE / LIST fields equal their PRESENT bytes.  A table entry with end 0 is
+ *   present (the getter returns zero, no error), one with end > dataSize is absent; unsorted or
+ *   duplicate tables give what the reference's binary search gives.  The words are 0 for a row whose
+ *   message did not open (a failing OpenMessageErr / MessageErr / OpenItemErr, an empty or panicked
+ *   range, a sub-message row whose owner has no such field); a row that is SPEC_STATUS_PANIC only
+ *   because a struct or any getter would panic keeps its bits.  Bits at or above the direct-field
+ *   count are 0;
  *   STATUS uint8: records OpenMessageErr's class; sub-messages MessageErr's class (0 if absent);
  *   list items OpenItemErr's class or SPEC_STATUS_PANIC (Go panics: element start > end);
  *   list values / structs SPEC_STATUS_INVALID_VALUE when GetErr fails; any row whose struct or
  *   any field would make Go panic (slice out of range) SPEC_STATUS_PANIC.
- * Encode input uses the same columns (STATUS, ERRMASK, TYPE ignored): scalars and structs are always written,
- * MESSAGE / LIST fields when PRESENT is non-zero (a present list may be empty), ANY when its span
- * is non-empty (FieldWriter.Any copies the bytes: internal/writer/writer.go:438-456). */
+ * Encode input uses the same columns (STATUS, ERRMASK, TYPE ignored): scalars and structs are written
+ * always, unless flagged SPEC_TREE_FIELD_OPTIONAL: such a field is written exactly when its HASMASK
+ * bit is set (a struct whole or not at all), and the columns of an absent one are never read (a
+ * garbage span there is no error and touches no heap).  MESSAGE / LIST fields are written when
+ * PRESENT is non-zero (a present list may be empty), ANY when its span is non-empty
+ * (FieldWriter.Any copies the bytes: internal/writer/writer.go:438-456); the mask's bits for
+ * those fields, and bits at or above the field count, are ignored.  The row's table holds the
+ * written fields in the Writer's tie-sorted order, IsBigMessage is per row over the written tags
+ * and the data size, and a row with nothing written is 00 00 50.  HASMASK is an input column:
+ * required when its table has rows. */
 #define SPEC_TREE_MAX_FIELDS 1024
 #define SPEC_TREE_MAX_TABLES 128
 #define SPEC_TREE_MAX_COLUMNS 2048
@@ -209,8 +228,16 @@ typedef struct spec_tree_field {
     uint8_t kind;    /* spec_kind */
     uint8_t elem;    /* SPEC_KIND_LIST: element kind (a scalar kind, STRUCT or MESSAGE) */
     int16_t parent;  /* enclosing field, -1 = the record */
-    uint16_t reserved;
+    uint16_t reserved; /* flags: SPEC_TREE_FIELD_OPTIONAL; every other bit 0 */
 } spec_tree_field;
+
+/* spec_tree_field.reserved bit 0: the field has presence (HasX() / a Write() that may skip its
+ * setter).  Valid on a direct field of a MESSAGE-shaped table (the records, a sub-message, a
+ * message-list item) whose kind is a scalar kind or STRUCT; anywhere else (a MESSAGE, LIST or ANY
+ * field, a struct member, a member of a struct list), like any other bit of `reserved`,
+ * spec_tree_layout and every entry point that validates a tree answer SPEC_E_INVALID_ARGUMENT.
+ * A table with such a field gets a HASMASK column; the layout of an unflagged tree is unchanged. */
+#define SPEC_TREE_FIELD_OPTIONAL 1u
 
 typedef struct spec_tree {
     uint32_t nfields;
@@ -221,7 +248,7 @@ typedef enum spec_tree_rel { SPEC_REL_ROOT = 0, SPEC_REL_ONE = 1, SPEC_REL_MANY 
 typedef enum spec_tree_shape { SPEC_SHAPE_MESSAGE = 0, SPEC_SHAPE_VALUE = 1, SPEC_SHAPE_STRUCT = 2 } spec_tree_shape;
 typedef enum spec_tree_role {
     SPEC_COL_VALUE = 0, SPEC_COL_PRESENT = 1, SPEC_COL_BEGIN = 2, SPEC_COL_STATUS = 3,
-    SPEC_COL_ERRMASK = 4, SPEC_COL_TYPE = 5
+    SPEC_COL_ERRMASK = 4, SPEC_COL_TYPE = 5, SPEC_COL_HASMASK = 6
 } spec_tree_role;
 
 typedef struct spec_tree_table {

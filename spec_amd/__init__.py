@@ -17,7 +17,7 @@ from .pipeline import HostDecoder
 from .nested import (NestedColumns, NestedDecoder, NestedEncoder, decode_nested, decode_nested_frames,
                      encode_nested, encode_nested_frames)
 from .schema import FLAT16, NESTED, Field, Kind, NestedSchema, Schema
-from .tree import (ListOf, Message, Struct, Tree, TreeColumns, TreeDecoder, TreeEncoder, decode_tree, decode_tree_frames,
+from .tree import (ListOf, Message, Opt, Struct, Tree, TreeColumns, TreeDecoder, TreeEncoder, decode_tree, decode_tree_frames,
                    decode_values, encode_tree, encode_tree_frames, pkg1_message, pkg1_tree, tree_rows)
 
 __all__ = [
@@ -25,7 +25,7 @@ __all__ = [
     "decode_flat", "decode_flat_errors", "encode_flat", "encode_flat_frames", "parse_messages", "PARSE_MESSAGE", "PARSE_LIST", "PARSE_VALUE",
     "FLAT16", "Field", "Kind", "Schema",
     "NESTED", "NestedSchema", "NestedColumns", "NestedDecoder", "NestedEncoder", "decode_nested",
-    "encode_nested", "encode_nested_frames", "ListOf", "Message", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
+    "encode_nested", "encode_nested_frames", "ListOf", "Message", "Opt", "Struct", "Tree", "TreeColumns", "TreeDecoder", "TreeEncoder", "decode_tree",
     "decode_values", "encode_tree", "encode_tree_frames", "pkg1_message", "pkg1_tree", "tree_rows",
     "decode_frames_errors", "decode_nested_frames", "decode_tree_frames",
     "decode_flat_present", "decode_frames_present", "encode_flat_present",

@@ -125,6 +125,10 @@ void gen_message_table(std::ostringstream &o, const TreeDesc &D, uint32_t t, con
       << "      uint64_t *errp = " << (T.err_col >= 0 ? "(uint64_t *)" + col_expr(T.err_col) : std::string("nullptr"))
       << ";\n"
       << "      uint64_t errs = 0;\n";
+    // HASMASK (a table with an optional field): bit k = the lookup found field k, end >= 0 (not
+    // the scalars' end <= 0 "no value" test: an entry with end 0 is present)
+    const bool hm = T.has_col >= 0;
+    if (hm) o << "      uint64_t has = 0;\n";
     // the scalar fields first, as straight-line code (the kernel runs only with every column
     // present): every table read and value window of the table issued before any decode, so
     // the LDS round trips overlap; windows are read for the type a Writer emits, and a field of
@@ -169,6 +173,7 @@ void gen_message_table(std::ostringstream &o, const TreeDesc &D, uint32_t t, con
         const std::string bit = k < 64 ? "(1ull << " + std::to_string(k) + ")" : "0ull";
         o << "      store_value_k<" << (int)F.kind << ">(" << col_expr(F.col) << ", row, v" << k << ");\n"
           << "      errs |= (ok" << k << " || end" << k << " <= 0) ? 0ull : " << bit << ";\n";
+        if (hm) o << "      has |= end" << k << " >= 0 ? " << bit << " : 0ull;\n";
     }
     for (uint32_t k = 0; k < T.nd; k++) {
         const uint32_t fi = D.direct[T.d0 + k];
@@ -177,6 +182,7 @@ void gen_message_table(std::ostringstream &o, const TreeDesc &D, uint32_t t, con
         const std::string bit = k < 64 ? "(1ull << " + std::to_string(k) + ")" : "0ull";
         o << "      { // field " << fi << " tag " << F.tag << " kind " << (int)F.kind << "\n"
           << "        const long long end = tree_end<" << F.rank << ">(s, o);\n";
+        if (hm) o << "        has |= end >= 0 ? " << bit << " : 0ull;\n";
         switch (F.kind) {
         case spec::K_MESSAGE:
             o << "        const long long e = end >= 0 ? ds + end : ds;\n"
@@ -230,7 +236,7 @@ void gen_message_table(std::ostringstream &o, const TreeDesc &D, uint32_t t, con
         o << "      }\n";
     }
     if (sel) {
-        o << "      (void)errp;\n      ro.errs = errs;\n"
+        o << "      (void)errp;\n      ro.errs = errs;\n" << (hm ? "      ro.has = has;\n" : "")
           << "    } else {\n"
           << "      st = " << fallback << "(s, D, B, " << t << "u, row, tlo, thi, gr);\n"
           << "    }\n"
@@ -238,8 +244,9 @@ void gen_message_table(std::ostringstream &o, const TreeDesc &D, uint32_t t, con
           << "  }\n";
         return;
     }
-    o << "      if (errp) errp[row] = errs;\n"
-      << "    } else {\n"
+    o << "      if (errp) errp[row] = errs;\n";
+    if (hm) o << "      if (" << col_expr(T.has_col) << ") ((uint64_t *)" << col_expr(T.has_col) << ")[row] = has;\n";
+    o << "    } else {\n"
       << "      st = " << fallback << "(s, D, B, " << t << "u, row, tlo, thi, gr);\n"
       << "    }\n"
       << "    store_u8(" << col_expr(T.status_col) << ", row, " << (root ? "panic ? (uint32_t)ST_PANIC : st" : "st")
@@ -274,12 +281,35 @@ void gen_table_trailer(std::ostringstream &o, const TreeDesc &D, const TTable &T
 // list elements are children written by their tables' later launches into the gaps skipped here.
 // the column reads of direct field k of table T issued before the first byte (values; a
 // sub-message's or list's presence; a sub-message's size)
+// An optional direct field (SPEC_TREE_FIELD_OPTIONAL) in the generated writers: a compile-time
+// fact per field.  Its presence test is bit k of the row's HASMASK word `hw` (gen_has_word: a
+// table of up to 64 fields has one word), or the run-time lookup for a wider table; its column
+// reads, its size and its bytes all sit behind the test, so an absent field's columns are never
+// read.  An unflagged field's code is what it was.
+std::string has_expr(const TreeDesc &D, const TTable &T, uint32_t k) {
+    if (T.nd <= 64) return "((hw >> " + std::to_string(k) + ") & 1)";
+    return "has_bit(B, D, D.t[" + std::to_string(&T - D.t) + "], row, " + std::to_string(k) + "u)";
+}
+void gen_has_word(std::ostringstream &o, const TTable &T, const char *ind) {
+    if (T.has_col >= 0 && T.nd <= 64)
+        o << ind << "const uint64_t hw = ((const uint64_t *)" << col_expr(T.has_col) << ")[row];\n" << ind << "(void)hw;\n";
+}
+// the load of a column element into v (declared here); of an optional field only when present
+void gen_load(std::ostringstream &o, const std::string &v, int kind, int col, const std::string &opt, const char *ind) {
+    if (opt.empty()) {
+        o << ind << "uint64_t " << v << "[4];\n" << ind << "load_value_k<" << kind << ">(" << col_expr(col) << ", row, " << v
+          << ");\n";
+        return;
+    }
+    o << ind << "uint64_t " << v << "[4] = {0, 0, 0, 0};\n"
+      << ind << "if (" << opt << ") load_value_k<" << kind << ">(" << col_expr(col) << ", row, " << v << ");\n";
+}
+
 void gen_field_loads(std::ostringstream &o, const TreeDesc &D, const TTable &T, uint32_t k, bool eager, const char *ind) {
     const TField &F = D.f[D.direct[T.d0 + k]];
+    const std::string opt = F.opt ? has_expr(D, T, k) : std::string();
     if ((F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) || F.kind == spec::K_ANY) {
-        if (eager)
-            o << ind << "uint64_t a" << k << "[4];\n" << ind << "load_value_k<" << (int)F.kind << ">(" << col_expr(F.col)
-              << ", row, a" << k << ");\n";
+        if (eager) gen_load(o, "a" + std::to_string(k), F.kind, F.col, opt, ind);
     } else if (F.kind == spec::K_MESSAGE || F.kind == spec::K_LIST)
         o << ind << "const uint32_t pr" << k << " = ((const uint8_t *)" << col_expr(F.present) << ")[row];\n";
     if (F.kind == spec::K_MESSAGE) o << ind << "const uint32_t sz" << k << " = B.size[" << F.table << "][row];\n";
@@ -287,9 +317,7 @@ void gen_field_loads(std::ostringstream &o, const TreeDesc &D, const TTable &T, 
     if (F.kind == spec::K_STRUCT && eager) {
         const uint32_t fi = D.direct[T.d0 + k];
         for (uint32_t i = fi + 1; i < F.send; i++)
-            if (D.f[i].kind != spec::K_STRUCT)
-                o << ind << "uint64_t m" << i << "[4];\n" << ind << "load_value_k<" << (int)D.f[i].kind << ">("
-                  << col_expr(D.f[i].col) << ", row, m" << i << ");\n";
+            if (D.f[i].kind != spec::K_STRUCT) gen_load(o, "m" + std::to_string(i), D.f[i].kind, D.f[i].col, opt, ind);
     }
     // a list's element range [begin[row], begin[row + 1]) (the size pass checked BEGIN)
     if (F.kind == spec::K_LIST)
@@ -363,10 +391,9 @@ void gen_struct_size(std::ostringstream &o, const TreeDesc &D, uint32_t sf, cons
 void gen_field_write(std::ostringstream &o, const TreeDesc &D, const TTable &T, uint32_t k, bool eager) {
     const uint32_t fi = D.direct[T.d0 + k];
     const TField &F = D.f[fi];
-    auto load = [&](const char *ind) {
-        o << ind << "uint64_t a" << k << "[4];\n" << ind << "load_value_k<" << (int)F.kind << ">(" << col_expr(F.col)
-          << ", row, a" << k << ");\n";
-    };
+    auto load = [&](const char *ind) { gen_load(o, "a" + std::to_string(k), F.kind, F.col, "", ind); };
+    // (an optional field: the whole block behind its presence test; a wide table's load sits inside)
+    const std::string open = F.opt ? "  if (" + has_expr(D, T, k) + ") {\n" : "  {\n";
     const std::string ev = eager ? "e" + std::to_string(k) : "ends_[" + std::to_string(k) + "]";
     const std::string mark = "    " + ev + " = (uint32_t)(em.pos - start);\n    nf++;\n" +
                              (F.tag > 255 ? "    bigtag = true;\n" : "");
@@ -374,7 +401,7 @@ void gen_field_write(std::ostringstream &o, const TreeDesc &D, const TTable &T, 
     else o << "  ends_[" << k << "] = 0xffffffffu; // field " << fi << " tag " << F.tag << "\n";
     if (F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) {
         const bool heap = F.kind == spec::K_STRING || F.kind == spec::K_BYTES;
-        o << "  {\n";
+        o << open;
         if (!eager) load("    ");
         o << "    emit_value_k<" << (int)F.kind << ">(em, a" << k << ", "
           << (heap ? "B.heaps[" + std::to_string(F.col) + "], B.heap_lens[" + std::to_string(F.col) + "]" : "nullptr, 0")
@@ -384,9 +411,16 @@ void gen_field_write(std::ostringstream &o, const TreeDesc &D, const TTable &T, 
         o << "  if ((uint32_t)(a" << k << "[0] >> 32)) {\n    emit_value_k<" << (int)F.kind << ">(em, a" << k
           << ", B.heaps[" << F.col << "], B.heap_lens[" << F.col << "]);\n" << mark << "  }\n";
     } else if (F.kind == spec::K_STRUCT) {
-        if (eager) gen_struct_emit(o, D, fi, 0, "  ");
-        else o << "  emit_struct(em, B, D, " << fi << "u, row);\n";
-        o << "  {\n" << mark << "  }\n";
+        if (F.opt) {
+            o << open;
+            if (eager) gen_struct_emit(o, D, fi, 0, "    ");
+            else o << "    emit_struct(em, B, D, " << fi << "u, row);\n";
+            o << mark << "  }\n";
+        } else {
+            if (eager) gen_struct_emit(o, D, fi, 0, "  ");
+            else o << "  emit_struct(em, B, D, " << fi << "u, row);\n";
+            o << "  {\n" << mark << "  }\n";
+        }
     } else if (F.kind == spec::K_MESSAGE) {
         o << "  if (pr" << k << ") {\n    B.pos[" << F.table << "][row] = em.pos;\n    em.skip(sz" << k << ");\n" << mark
           << "  } else {\n    B.pos[" << F.table << "][row] = ~0ull; // absent: its row is not written\n  }\n";
@@ -416,6 +450,7 @@ void gen_write_table(std::ostringstream &o, const TreeDesc &D, uint32_t t) {
     const bool inl = eager && D.ntables <= 32;
     o << "template <class E>\n__device__ " << (inl ? "__forceinline__" : "__noinline__") << " void gen_wrow_" << t
       << "(E &em, const TreeDesc &D, const TreeBufs &B, uint64_t row, uint64_t start) {\n";
+    gen_has_word(o, T, "  ");
     for (uint32_t k = 0; k < T.nd; k++) gen_field_loads(o, D, T, k, eager, "  ");
     o << "  uint32_t nf = 0;\n  bool bigtag = false;\n";
     // field ends: registers (e<k>), or for a wide table an array the table loop reads at run time
@@ -463,11 +498,12 @@ void gen_size_table(std::ostringstream &o, const TreeDesc &D, uint32_t t) {
     o << "__device__ __forceinline__ void gen_srow_" << t
       << "(const TreeDesc &D, const TreeBufs &B, uint32_t x, uint64_t row, bool &err) {\n"
       << "  {\n";
+    // (a table of more than 64 fields reads its HASMASK words per optional field: has_expr)
+    gen_has_word(o, T, "    ");
     for (uint32_t k = 0; k < T.nd; k++) {
         const TField &F = D.f[D.direct[T.d0 + k]];
         if ((F.kind >= spec::K_BOOL && F.kind <= spec::K_BYTES) || F.kind == spec::K_ANY)
-            o << "    uint64_t a" << k << "[4];\n    load_value_k<" << (int)F.kind << ">(" << col_expr(F.col) << ", row, a" << k
-              << ");\n";
+            gen_load(o, "a" + std::to_string(k), F.kind, F.col, F.opt ? has_expr(D, T, k) : std::string(), "    ");
         else if (F.kind == spec::K_MESSAGE || F.kind == spec::K_LIST)
             o << "    const uint32_t pr" << k << " = ((const uint8_t *)" << col_expr(F.present) << ")[row];\n";
         if (F.kind == spec::K_STRUCT) gen_field_loads(o, D, T, k, true, "    ");
@@ -489,6 +525,7 @@ void gen_size_table(std::ostringstream &o, const TreeDesc &D, uint32_t t) {
                                (tile ? " bm |= 1ull << " + std::to_string(k) + ";" : std::string());
         for (int bl = 0; tile && bl < spec::TREE_TILE_W; bl++) // blocks ending before field k
             if (cut[bl + 1] == k) o << "    const uint64_t tb" << bl << " = data;\n";
+        if (F.opt) o << "    if (" << has_expr(D, T, k) << ") { // optional: sized when present\n";
         switch (F.kind) {
         case spec::K_MESSAGE:
             o << "    if (pr" << k << ") { data += B.size[" << F.table << "][row]; nf++;" << tg << " }\n";
@@ -529,6 +566,7 @@ void gen_size_table(std::ostringstream &o, const TreeDesc &D, uint32_t t) {
             o << "    data += " << sz << "; nf++;" << tg << "\n";
         }
         }
+        if (F.opt) o << "    }\n";
     }
     if (tile) {
         for (int bl = 0; bl < spec::TREE_TILE_W; bl++)
@@ -659,7 +697,7 @@ void gen_pair_rows(std::ostringstream &o, const TreeDesc &D, uint32_t x, int P) 
       << "  uint2 *gr = (uint2 *)(smem + slab) + (threadIdx.x & 63);\n"
       << "  uint4 *xch = (uint4 *)(smem + slab + slots);\n"
       << "  (void)rpw;\n"
-      << "  tree_rows_pair<" << P << ">(B, x, rows, slab, xch,\n"
+      << "  tree_rows_pair<" << P << (T.has_col >= 0 ? ", true" : "") << ">(B, x, rows, slab, xch,\n"
       << "    [&](const TreeLds &s, uint64_t row, long long lo, long long hi, RowOut &ro) {\n"
       << call.str() << "    },\n"
       << "    [&](const GlobalSrc &s, uint64_t row, long long lo, long long hi, RowOut &ro) {\n"
@@ -667,6 +705,9 @@ void gen_pair_rows(std::ostringstream &o, const TreeDesc &D, uint32_t x, int P) 
       << "    [&](uint64_t row, bool panic, const RowOut &a, const RowOut &b) {\n"
       << "      uint64_t *errp = " << (T.err_col >= 0 ? "(uint64_t *)" + col_expr(T.err_col) : std::string("nullptr")) << ";\n"
       << "      if (a.fast && errp) errp[row] = a.errs | b.errs;\n"
+      << (T.has_col >= 0 ? "      if (a.fast && " + col_expr(T.has_col) + ") ((uint64_t *)" + col_expr(T.has_col) +
+                               ")[row] = a.has | b.has;\n"
+                         : std::string())
       << "      const uint32_t st = a.st == ST_PANIC || b.st == ST_PANIC ? (uint32_t)ST_PANIC : a.st;\n"
       << "      store_u8(" << col_expr(T.status_col) << ", row, panic ? (uint32_t)ST_PANIC : st);\n"
       << "    });\n"
@@ -751,6 +792,7 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
           << "  const uint64_t off = " << (b ? "B.tblk[row * " + std::to_string(TILE_W) + " + " + std::to_string(b - 1) + "]" : "0")
           << ", data = B.tblk[row * " << TILE_W << " + " << TILE_W - 1 << "];\n"
           << "  const uint64_t m = B.tmask[row];\n";
+        gen_has_word(o, T, "  ");
         for (uint32_t k = cut[b]; k < cut[b + 1]; k++) gen_field_loads(o, D, T, k, true, "  ");
         if (b == 0) o << "  if (B.ends_out) B.ends_out[row] = start + B.size[0][row];\n";
         o << "  const bool big = (m & 0x" << std::hex << bigm << std::dec << "ull) != 0 || (m != 0 && data > 65535);\n"
@@ -784,6 +826,10 @@ void gen_tile(std::ostringstream &o, const TreeDesc &D) {
         o << "template <class Mk>\n__device__ __forceinline__ void gen_trow_" << x
           << "(const Mk &mk, const TreeDesc &D, const TreeBufs &B, uint64_t row) {\n";
         if (X.shape == spec::SHAPE_MESSAGE) {
+            // (the row's HASMASK word and the loads behind it are issued with the position, before the
+            // unplaced-row test: in bounds, bind_columns requires the column wherever the table has
+            // rows; the mask of a row no owner placed is read and ignored)
+            gen_has_word(o, X, "  ");
             for (uint32_t k = 0; k < X.nd; k++) gen_field_loads(o, D, X, k, true, "  ");
             o << "  const uint64_t start = B.pos[" << x << "][row];\n"
               << "  if (start == ~0ull) { gen_unplace_" << x << "(D, B, row); return; }\n"

@@ -49,6 +49,8 @@ __global__ __launch_bounds__(TB) void tree_size_kernel(const TreeDesc *Dp, const
                 if (F.kind == K_MESSAGE || F.kind == K_LIST) {
                     if (!cell(B, D, F.present, row)[0]) continue;
                     sz = F.kind == K_MESSAGE ? B.size[F.table][row] : list_size(B, D, F.table, row, err).total;
+                } else if (F.opt && !has_bit(B, D, T, row, k)) {
+                    continue; // an absent optional field: its columns are not read
                 } else if (F.kind == K_STRUCT) {
                     sz = struct_size(B, D, D.direct[T.d0 + k], row, err);
                 } else {
@@ -134,6 +136,8 @@ __global__ __launch_bounds__(TB) void tree_write_kernel(const TreeDesc *Dp, cons
                     em.rvarint((uint64_t)L.count * (L.big ? 4 : 2));
                     em.put1(L.big ? T_BIG_LIST : T_LIST);
                 }
+            } else if (F.opt && !has_bit(B, D, T, row, k)) {
+                continue;
             } else if (F.kind == K_STRUCT) {
                 emit_struct(em, B, D, fi, row);
             } else {
@@ -297,6 +301,13 @@ bool build_layout(const spec_tree *tr, Layout &L) {
             return false;
         if (k == SPEC_KIND_LIST && !is_scalar(f[i].elem) && f[i].elem != SPEC_KIND_STRUCT && f[i].elem != SPEC_KIND_MESSAGE)
             return false;
+        // SPEC_TREE_FIELD_OPTIONAL: a scalar or struct that is a direct field of a message (the
+        // record, a sub-message, a message-list item); no other bit of `reserved`
+        if (f[i].reserved & ~SPEC_TREE_FIELD_OPTIONAL) return false;
+        const bool opt = (f[i].reserved & SPEC_TREE_FIELD_OPTIONAL) != 0;
+        if (opt && !is_scalar(k) && k != SPEC_KIND_STRUCT) return false;
+        if (opt && p >= 0 && f[p].kind != SPEC_KIND_MESSAGE && !(f[p].kind == SPEC_KIND_LIST && f[p].elem == SPEC_KIND_MESSAGE))
+            return false;
         if (p >= 0) {
             const int pk = f[p].kind;
             if (pk != SPEC_KIND_STRUCT && pk != SPEC_KIND_MESSAGE && pk != SPEC_KIND_LIST) return false;
@@ -313,6 +324,7 @@ bool build_layout(const spec_tree *tr, Layout &L) {
         F.parent = (int16_t)p;
         F.table = F.col = F.present = -1;
         F.send = (uint16_t)(i + 1);
+        F.opt = opt ? 1 : 0;
     }
     // subtree ends (pre-order: a field's descendants follow it) and struct nesting depth
     for (uint32_t i = 0; i < nf; i++) {
@@ -433,6 +445,12 @@ bool build_layout(const spec_tree *tr, Layout &L) {
         // ERRMASK: a bit per direct field, ceil(nd / 64) words (at least one)
         if (t.shape == SPEC_SHAPE_MESSAGE &&
             (T.err_col = (int16_t)add_col(L, x, d, SPEC_COL_ERRMASK, 0, 8 * std::max<uint32_t>(1, (T.nd + 63) / 64))) < 0)
+            return false;
+        // HASMASK: ERRMASK's words again, only where a direct field is optional
+        T.has_col = -1;
+        bool any_opt = false;
+        for (uint32_t k = 0; t.shape == SPEC_SHAPE_MESSAGE && k < T.nd; k++) any_opt = any_opt || D.f[D.direct[T.d0 + k]].opt;
+        if (any_opt && (T.has_col = (int16_t)add_col(L, x, d, SPEC_COL_HASMASK, 0, 8 * std::max<uint32_t>(1, (T.nd + 63) / 64))) < 0)
             return false;
         if ((T.status_col = (int16_t)add_col(L, x, d, SPEC_COL_STATUS, 0, 1)) < 0) return false;
         t.ncolumns = (uint16_t)(L.nc - t.first_column);
@@ -559,7 +577,8 @@ int bind_columns(const Layout &L, const EncWs &w, uint8_t *ws, const void *const
         // a BEGIN column has owner rows + 1 entries: needed whenever the owner table has rows
         // (an owner whose lists are all empty still reads begin[row], begin[row + 1])
         const uint64_t col_rows = col.role == SPEC_COL_BEGIN ? rows[L.tables[col.table].parent] : rows[col.table];
-        const bool input = col.role == SPEC_COL_VALUE || col.role == SPEC_COL_PRESENT || col.role == SPEC_COL_BEGIN;
+        const bool input = col.role == SPEC_COL_VALUE || col.role == SPEC_COL_PRESENT || col.role == SPEC_COL_BEGIN ||
+                           col.role == SPEC_COL_HASMASK;
         if (input && !columns[c] && col_rows) return SPEC_E_INVALID_ARGUMENT;
         if (spans && rows[col.table] && !B.heaps[c]) return SPEC_E_INVALID_ARGUMENT;
     }

@@ -41,7 +41,7 @@ struct TField {
     uint16_t nmem, mem0; // STRUCT / LIST<STRUCT>: members[mem0 .. mem0 + nmem)
     uint16_t send;       // one past the last field of this field's subtree (pre-order)
     uint8_t nested;      // STRUCT / LIST<STRUCT>: some member is itself a struct
-    uint8_t pad;
+    uint8_t opt;         // SPEC_TREE_FIELD_OPTIONAL: written when its bit of the table's HASMASK is set
 };
 
 struct TTable {
@@ -50,7 +50,7 @@ struct TTable {
     int16_t begin_col, status_col;
     uint16_t nd, d0; // MESSAGE shape: direct[d0 .. d0 + nd) (write order), sorted[...] (table order)
     int16_t err_col; // MESSAGE shape: ERRMASK column
-    int16_t pad2;
+    int16_t has_col; // MESSAGE shape with an optional direct field: HASMASK column (ERRMASK's width), else -1
     // decode groups: a group root (the records or a list table) and the sub-message tables
     // hanging off it 1:1, decoded in one pass (tree_decode.hip)
     uint16_t groot;  // this table's group root
@@ -525,6 +525,12 @@ __device__ __forceinline__ uint64_t struct_size(const TreeBufs &B, const TreeDes
     while (d > 0) close();
     if (acc[0] > MAX_SIZE) err = true;
     return acc[0] + vlen64(acc[0]) + 1;
+}
+
+// Bit k of row `row`'s HASMASK words (table T has the column): the k-th direct field is present
+__device__ __forceinline__ bool has_bit(const TreeBufs &B, const TreeDesc &D, const TTable &T, uint64_t row, uint32_t k) {
+    const uint64_t *w = (const uint64_t *)B.cols[T.has_col] + row * ((uint32_t)D.width[T.has_col] / 8);
+    return (w[k >> 6] >> (k & 63)) & 1;
 }
 
 // [begin[row], begin[row + 1]) of list table y, from its BEGIN column (checked)

@@ -413,7 +413,11 @@ bool launch_group(const DecCall &c, uint32_t x) {
         rpw = 64;
         void *args[] = {(void *)&c.Dd, (void *)&c.Bd, &xx, &slab, &slots, &rpw};
         const unsigned grid = (unsigned)std::min<uint64_t>((cap + 63) / 64, 1u << 20);
-        return launch_tree_fn(c.gen[TREE_FN_GROUP_PAIR + x], grid, 1, 64 * P, slab + slots + (P - 1) * 1024, c.st, args);
+        // (a root table with a HASMASK column: 512 B more per extra wave for the HasField bits;
+        // pkg1 with presence: 38.5 KiB per block, still four blocks in a CU's 160 KiB)
+        const uint32_t xhas = d->L.desc.t[x].has_col >= 0 ? (P - 1) * 512 : 0;
+        return launch_tree_fn(c.gen[TREE_FN_GROUP_PAIR + x], grid, 1, 64 * P, slab + slots + (P - 1) * 1024 + xhas, c.st,
+                              args);
     }
     if (c.gen && c.gen[TREE_FN_GROUP + x]) {
         void *args[] = {(void *)&c.Dd, (void *)&c.Bd, &xx, &slab, &wb, &rpw};

@@ -138,6 +138,7 @@ __device__ __forceinline__ void tree_rows(const TreeBufs &B, uint32_t x, uint64_
 struct RowOut {
     uint64_t errs;
     uint32_t st, fast;
+    uint64_t has; // HasField bits of that wave's fields (a root table with a HASMASK column)
 };
 
 // tree_rows for a group of P waves (a 64 P-thread block): every wave takes the same 64 rows,
@@ -148,7 +149,10 @@ struct RowOut {
 // P waves per 64 rows at the same LDS per row: a SIMD holds P waves, so one's LDS round trips
 // overlap the others' decode.  Rows whose span exceeds the slab parse from HBM (the lane windows
 // of tree_rows are not used here).
-template <int P, class LdsBody, class GlobBody, class Fin>
+// HAS (the root table has a HASMASK column): the others' HasField bits travel the same way, in 64
+// uint2 entries per extra wave behind xch's (P - 1) * 64 entries; without it the block's LDS is
+// what it was.
+template <int P, bool HAS = false, class LdsBody, class GlobBody, class Fin>
 __device__ __forceinline__ void tree_rows_pair(const TreeBufs &B, uint32_t x, uint64_t rows, uint32_t slab_bytes,
                                                uint4 *xch, LdsBody lds_body, GlobBody glob_body, Fin fin) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -178,22 +182,29 @@ __device__ __forceinline__ void tree_rows_pair(const TreeBufs &B, uint32_t x, ui
         const bool span = slab_bytes && slo < shi && (uint64_t)st.granules * 16 + 16 <= (uint64_t)slab_bytes;
         if (span) stage_span<STREAM_AUX>(rsrc, slab, st, B.stream_len, lane, wave, P);
         __syncthreads(); // the slab is whole; the previous rows' exchange has been read
-        RowOut ro = {0, 0, 0};
+        RowOut ro = {0, 0, 0, 0};
         if (valid) {
             if (span)
                 lds_body(TreeLds{(lds_u8 *)slab, sb, (int)slab_bytes}, row, lo, hi, ro);
             else
                 glob_body(gs, row, lo, hi, ro);
         }
+        uint2 *xch2 = (uint2 *)(xch + (P - 1) * 64);
         if (wave) xch[(wave - 1) * 64 + lane] = make_uint4((uint32_t)ro.errs, (uint32_t)(ro.errs >> 32), ro.st, ro.fast);
+        if constexpr (HAS)
+            if (wave) xch2[(wave - 1) * 64 + lane] = make_uint2((uint32_t)ro.has, (uint32_t)(ro.has >> 32));
         __syncthreads(); // the others' outcomes are in xch; every wave is done with the slab
         if (wave == 0 && valid) {
-            RowOut r = {0, 0, 0};
+            RowOut r = {0, 0, 0, 0};
 #pragma unroll
             for (int w = 1; w < P; w++) {
                 const uint4 q = xch[(w - 1) * 64 + lane];
                 r.errs |= (uint64_t)q.x | ((uint64_t)q.y << 32);
                 r.st = q.z == ST_PANIC ? (uint32_t)ST_PANIC : r.st;
+                if constexpr (HAS) {
+                    const uint2 h = xch2[(w - 1) * 64 + lane];
+                    r.has |= (uint64_t)h.x | ((uint64_t)h.y << 32);
+                }
             }
             fin(row, panic, ro, r);
         }
@@ -244,12 +255,17 @@ __device__ __forceinline__ uint32_t tree_message_row_inl(const Src &s, const Tre
     // (the index pass runs with no columns: a null column stays null, not null + row * W)
     uint64_t *const ecol = T.err_col >= 0 ? (uint64_t *)B.cols[T.err_col] : nullptr;
     uint64_t *errp = ecol ? ecol + row * ((uint32_t)D.width[T.err_col] / 8) : nullptr;
-    uint64_t errs = 0;
+    // HASMASK (a table with an optional field): the same words, bit k = m.HasField(tag): the
+    // lookup finds the tag and its end lies within the data (no bit on a message that did not open)
+    uint64_t *const hcol = T.has_col >= 0 ? (uint64_t *)B.cols[T.has_col] : nullptr;
+    uint64_t *hasp = hcol ? hcol + row * ((uint32_t)D.width[T.has_col] / 8) : nullptr;
+    uint64_t errs = 0, has = 0;
     for (uint32_t k = 0; k < T.nd; k++) {
         const uint32_t fi = D.direct[T.d0 + k];
         const TField &F = D.f[fi];
         const long long end = rec_field_end(s, ri, F.tag, F.rank);
         const long long e = end >= 0 ? ds + end : ds;
+        if (end >= 0) has |= 1ull << (k & 63);
         bool bad = false; // the field's *Err getter errs
         switch (F.kind) {
         case K_MESSAGE: {
@@ -309,10 +325,12 @@ __device__ __forceinline__ uint32_t tree_message_row_inl(const Src &s, const Tre
         if (bad) errs |= 1ull << (k & 63);
         if ((k & 63) == 63 && k + 1 < T.nd) {
             if (errp) errp[k >> 6] = errs;
-            errs = 0;
+            if (hasp) hasp[k >> 6] = has;
+            errs = has = 0;
         }
     }
     if (errp) errp[T.nd ? (T.nd - 1) >> 6 : 0] = errs;
+    if (hasp) hasp[T.nd ? (T.nd - 1) >> 6 : 0] = has;
     return st;
 }
 

@@ -371,10 +371,12 @@ class SpecSet:
         kind, _, _ = self._lookup(pkg, typ)
         return Kind.INT32 if kind == "enum" else None
 
-    def tree(self, name: str, package: str = None, max_depth: int = 2):
+    def tree(self, name: str, package: str = None, max_depth: int = 2, presence: bool = False):
+        """presence: every scalar and struct field of every message is optional (a HASMASK column
+        per message table, spec_amd.tree)."""
         from .tree import Tree
 
-        return Tree(self.message(name, package), max_depth=max_depth)
+        return Tree(self.message(name, package), max_depth=max_depth, presence=presence)
 
 
 def load(text: str, package: str = "") -> SpecFile:

@@ -17,7 +17,9 @@ field (a row per owner row) and one per list field (a row per element, CSR `#beg
 names: `a.b` (a field), `a.b.m` (struct member), `l[]` (value list elements), `l[].x` (item
 field / struct member), `a?` (HasField of a message or list field), `l#begin`, `<table>#status`
 (`#status` for the records), `<table>#errmask` (per message row: bit k = the k-th direct
-field's *Err getter errs), `a#type` (Value.Type() of an `any` field).
+field's *Err getter errs), `a#type` (Value.Type() of an `any` field), `<table>#hasmask` (only a
+message table with an optional field — `Opt(type)`, or `Tree(..., presence=True)`: bit k =
+HasField of the k-th direct field; the encoder writes an optional field when its bit is set).
 """
 from __future__ import annotations
 
@@ -34,8 +36,9 @@ from .schema import WIDTH, Kind
 SCALARS = tuple(Kind(k) for k in range(1, 16))
 REL_ROOT, REL_ONE, REL_MANY = 0, 1, 2
 SHAPE_MESSAGE, SHAPE_VALUE, SHAPE_STRUCT = 0, 1, 2
-ROLE_VALUE, ROLE_PRESENT, ROLE_BEGIN, ROLE_STATUS, ROLE_ERRMASK, ROLE_TYPE = 0, 1, 2, 3, 4, 5
-INPUT_ROLES = (ROLE_VALUE, ROLE_PRESENT, ROLE_BEGIN)  # what spec_encode_tree reads
+ROLE_VALUE, ROLE_PRESENT, ROLE_BEGIN, ROLE_STATUS, ROLE_ERRMASK, ROLE_TYPE, ROLE_HASMASK = 0, 1, 2, 3, 4, 5, 6
+INPUT_ROLES = (ROLE_VALUE, ROLE_PRESENT, ROLE_BEGIN, ROLE_HASMASK)  # what spec_encode_tree reads
+FIELD_OPTIONAL = 1  # spec_tree_field.reserved: SPEC_TREE_FIELD_OPTIONAL
 
 
 class Struct:
@@ -66,6 +69,13 @@ class ListOf:
     elem: object  # Kind (scalar), Struct or Message
 
 
+@dataclass(frozen=True)
+class Opt:
+    """A message field's type with presence (HasX(), a Write() that may skip the setter): a scalar
+    Kind or a Struct.  The field's table gets a `#hasmask` column."""
+    type: object
+
+
 @dataclass
 class TreeField:
     path: str
@@ -73,6 +83,7 @@ class TreeField:
     kind: Kind
     elem: int = 0
     parent: int = -1
+    optional: bool = False
 
 
 @dataclass
@@ -101,12 +112,18 @@ class Tree:
     """A record message flattened into spec_tree fields (pre-order), with its table/column layout
     from spec_tree_layout."""
 
-    def __init__(self, root: Message, max_depth: int = 2):
+    def __init__(self, root: Message, max_depth: int = 2, presence: bool = False):
+        """presence: every eligible field (a scalar or struct directly in a message) is optional,
+        as if declared Opt(type)."""
         self.root = root
         self.fields: list[TreeField] = []
+        self._presence = bool(presence)
         self._add_message(root, -1, "", {root.name: 1}, max_depth)
         if len(self.fields) > _lib.SPEC_TREE_MAX_FIELDS:
             raise ValueError("tree too large")
+        self._bind()
+
+    def _bind(self):
         c = _lib.SpecTree()
         c.nfields = len(self.fields)
         for i, f in enumerate(self.fields):
@@ -114,34 +131,42 @@ class Tree:
             c.fields[i].kind = int(f.kind)
             c.fields[i].elem = int(f.elem)
             c.fields[i].parent = f.parent
+            c.fields[i].reserved = FIELD_OPTIONAL if f.optional else 0
         self.c = c
         self._layout()
 
     @classmethod
     def from_fields(cls, fields):
-        """A tree from flattened fields [(path, tag, kind, elem, parent), ...] (pre-order)."""
+        """A tree from flattened fields [(path, tag, kind, elem, parent[, optional]), ...] (pre-order)."""
         t = cls.__new__(cls)
         t.root = None
-        t.fields = [TreeField(p, tag, Kind(k), int(e), par) for p, tag, k, e, par in fields]
-        c = _lib.SpecTree()
-        c.nfields = len(t.fields)
-        for i, f in enumerate(t.fields):
-            c.fields[i].tag, c.fields[i].kind, c.fields[i].elem, c.fields[i].parent = f.tag, int(f.kind), f.elem, f.parent
-        t.c = c
-        t._layout()
+        t.fields = [TreeField(f[0], f[1], Kind(f[2]), int(f[3]), f[4], bool(f[5]) if len(f) > 5 else False)
+                    for f in fields]
+        t._bind()
         return t
 
     def to_fields(self):
-        return [(f.path, f.tag, int(f.kind), int(f.elem), f.parent) for f in self.fields]
+        """The flattened fields; a sixth element (1) only on optional fields."""
+        return [(f.path, f.tag, int(f.kind), int(f.elem), f.parent) + ((1,) if f.optional else ())
+                for f in self.fields]
+
+    def plain(self) -> "Tree":
+        """This tree with no field optional."""
+        return Tree.from_fields([f[:5] for f in self.to_fields()])
 
     # -- flattening --
-    def _add(self, path, tag, kind, elem=0, parent=-1):
-        self.fields.append(TreeField(path, tag, Kind(kind), int(elem), parent))
+    def _add(self, path, tag, kind, elem=0, parent=-1, optional=False):
+        self.fields.append(TreeField(path, tag, Kind(kind), int(elem), parent, bool(optional)))
         return len(self.fields) - 1
 
     def _add_message(self, msg, parent, prefix, depth, max_depth):
         for name, tag, typ in msg.fields:
             path = prefix + name
+            opt = self._presence
+            if isinstance(typ, Opt):
+                typ, opt = typ.type, True
+                if isinstance(typ, (ListOf, Message)) or typ == Kind.ANY:
+                    raise ValueError(f"{path}: Opt takes a scalar kind or a Struct")
             if isinstance(typ, ListOf):
                 e = typ.elem
                 if isinstance(e, Message):
@@ -164,10 +189,10 @@ class Tree:
                 d2[typ.name] = d2.get(typ.name, 0) + 1
                 self._add_message(typ, i, path + ".", d2, max_depth)
             elif isinstance(typ, Struct):
-                i = self._add(path, tag, Kind.STRUCT, 0, parent)
+                i = self._add(path, tag, Kind.STRUCT, 0, parent, opt)
                 self._add_members(typ, i, path + ".")
             else:
-                self._add(path, tag, Kind(typ), 0, parent)
+                self._add(path, tag, Kind(typ), 0, parent, opt and Kind(typ) != Kind.ANY)
 
     def _add_members(self, struct, parent, prefix):
         """A struct's members in declaration order (pre-order: a struct member's own members
@@ -205,6 +230,8 @@ class Tree:
                 name = f"{tb.path}#status"
             elif k.role == ROLE_ERRMASK:
                 name = f"{tb.path}#errmask"
+            elif k.role == ROLE_HASMASK:
+                name = f"{tb.path}#hasmask"
             elif k.role == ROLE_TYPE:
                 name = f"{f.path}#type"
             elif k.role == ROLE_PRESENT:
@@ -252,6 +279,8 @@ class TreeColumns:
             return a.reshape(-1)
         if c.role == ROLE_ERRMASK:
             return a.view(np.uint64).reshape(-1)
+        if c.role == ROLE_HASMASK:
+            return a.view(np.uint64).reshape(-1, c.width // 8)
         if c.role == ROLE_BEGIN:
             return a.view(np.uint32).reshape(-1)
         return a
@@ -548,10 +577,10 @@ def pkg1_message(with_any: bool = True) -> Message:
 
 
 
-def pkg1_tree(max_depth: int = 2) -> Tree:
-    return Tree(pkg1_message(), max_depth=max_depth)
+def pkg1_tree(max_depth: int = 2, presence: bool = False) -> Tree:
+    return Tree(pkg1_message(), max_depth=max_depth, presence=presence)
 
 
-__all__ = ["Struct", "Message", "ListOf", "Tree", "TreeDecoder", "TreeEncoder", "TreeColumns", "decode_tree",
+__all__ = ["Struct", "Message", "ListOf", "Opt", "Tree", "TreeDecoder", "TreeEncoder", "TreeColumns", "decode_tree",
            "decode_values",
            "encode_tree", "encode_tree_frames", "tree_rows", "pkg1_message", "pkg1_tree", "WIDTH"]

@@ -172,11 +172,16 @@ def _any_values(rng, m):
     return as_bytes(spans, m), heap
 
 
-def tree_batch(tree, n: int, seed: int = SEED, count=(0, 4), present: float = 0.8, str_len=(0, 20)):
+def tree_batch(tree, n: int, seed: int = SEED, count=(0, 4), present: float = 0.8, str_len=(0, 20), has: float = 1.0):
     """Random columns for a spec_amd.Tree (canonical: a field under an absent sub-message or list
     holds zeros, so decode(encode(x)) == x up to span offsets).  Returns (cols {name: uint8
-    [entries, width]}, heaps {name: uint8[]}, rows per table)."""
-    from .tree import REL_MANY, REL_ONE, ROLE_BEGIN, ROLE_ERRMASK, ROLE_PRESENT, ROLE_STATUS, ROLE_TYPE
+    [entries, width]}, heaps {name: uint8[]}, rows per table).
+    has: the density of the HASMASK columns' bits for optional fields (a tree with presence); an
+    absent field's columns are zeroed.  The bits of the other fields are what a decode reports:
+    MESSAGE / LIST fields their PRESENT byte, an `any` field whether its span is non-empty, an
+    always-written field 1 (0 in a row under an absent sub-message)."""
+    from .tree import (REL_MANY, REL_ONE, ROLE_BEGIN, ROLE_ERRMASK, ROLE_HASMASK, ROLE_PRESENT, ROLE_STATUS, ROLE_TYPE,
+                       ROLE_VALUE)
 
     rng = np.random.default_rng(seed)
     T = tree.tables
@@ -206,6 +211,27 @@ def tree_batch(tree, n: int, seed: int = SEED, count=(0, 4), present: float = 0.
                 cols[c.name] = np.zeros((R, 1), np.uint8)
             elif c.role == ROLE_ERRMASK:
                 cols[c.name] = np.zeros((R, 8), np.uint8)  # values written by their own kinds: no errors
+            elif c.role == ROLE_HASMASK:
+                mask = np.zeros((R, c.width // 8), np.uint64)
+                direct = [i for i, f in enumerate(tree.fields) if f.parent == t.field]
+                for k, i in enumerate(direct):
+                    f = tree.fields[i]
+                    if f.kind in (Kind.MESSAGE, Kind.LIST):
+                        bit = cols[f"{f.path}?"].reshape(-1).astype(bool)
+                    elif f.kind == Kind.ANY:
+                        bit = cols[f.path].view(np.uint32).reshape(-1, 2)[:, 1] > 0
+                    elif f.optional:
+                        bit = (rng.random(R) < has) & live
+                        for vc in t.columns:  # the field's own column, or its struct's members'
+                            j = vc.field
+                            while j > i and tree.fields[j].kind != Kind.LIST:
+                                j = tree.fields[j].parent
+                            if vc.role == ROLE_VALUE and j == i:
+                                cols[vc.name][~bit] = 0
+                    else:
+                        bit = live
+                    mask[:, k // 64] |= bit.astype(np.uint64) << np.uint64(k % 64)
+                cols[c.name] = mask.view(np.uint8).reshape(R, c.width)
             elif c.role == ROLE_TYPE:  # Value.Type() of the any value before it: its last byte
                 v = tree.fields[c.field].path
                 sp, h = cols[v].view(np.uint32).reshape(-1, 2), heaps[v]
