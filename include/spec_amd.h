@@ -717,7 +717,13 @@ int spec_shard_host_decode(spec_shard *c, const uint8_t *stream_host, uint64_t s
  * 2,097,152 nested containers: records deeper than 32 are parsed again with their stacks in a
  * stream-ordered HBM scratch of the call, 64 MiB).  sizes[i] (optional) =
  * ParseMessage's size (bytes of the message), 0 on error.  head = bytes before each record
- * (4 for mpx frames, see spec_frames_index). */
+ * (4 for mpx frames, see spec_frames_index).  ends must be non-decreasing and end at or before
+ * stream_len; a record with ends[r] < ends[r-1] + head (a frame shorter than its head, or an end
+ * that steps back but stays within its group of 64 records' span) is empty.  A group of 64 records
+ * with an end outside that (past stream_len, beyond the group's last end or below its first start)
+ * has unspecified status and sizes for its own records; nothing else is touched: no byte outside
+ * [stream_bytes, stream_bytes + stream_len) is read, status[0, n) and sizes[0, n) alone are
+ * written, and every other group's records are as specified.  The same holds for spec_parse_batch. */
 int spec_parse_messages(const uint8_t *stream_bytes, uint64_t stream_len, const uint64_t *ends, uint64_t n,
                         uint32_t head, uint8_t *status, uint32_t *sizes, void *stream);
 

@@ -206,14 +206,17 @@ __global__ __launch_bounds__(256) void parse_kernel(DecodeArgs a, uint32_t *size
     load_group_ends(a, base, lane, lo, hi);
     const Group gr = make_group(a.n, base, lo, hi, a.slab);
     uint32_t st = ST_OK, size = 0;
-    if (gr.in_lds) {
-        stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
-        if (!valid) return;
+    // ends outside the contract (include/spec_amd.h: not non-decreasing, or past stream_len) can put a
+    // lane's record outside the span its group stages; its slab positions would then lie outside the
+    // slab.  Such a lane parses from HBM, where the buffer descriptor checks every read.
+    const bool staged = gr.rec_lo >= gr.st.origin && gr.rec_hi <= gr.st.origin + 16ull * gr.st.granules;
+    if (gr.in_lds) stage_span<STREAM_AUX>(rsrc, slab + SLAB_GUARD, gr.st, a.stream_len, lane);
+    if (!valid) return;
+    if (gr.in_lds && staged) {
         LdsSrc s{(lds_u8 *)slab};
         LocalStack stk;
         st = parse_record(s, gr.rs(), gr.re(), root, size, stk);
     } else {
-        if (!valid) return;
         GlobalSrc s{a.stream, a.stream_len};
         LocalStack stk;
         st = parse_record(s, (long long)gr.rec_lo, (long long)gr.rec_hi, root, size, stk);
